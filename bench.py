@@ -23,11 +23,18 @@ Workloads:
 
 Inputs come from the device generator (tmh_synth_sites_device), resident in
 HBM before timing starts.  Its host twin (tmlibrary_amd/synth.py) regenerates
-the same pixels, so the last step's results are compared against an oracle
-fingerprint committed under tests/golden/ (make_bench_fingerprint.py):
+the same pixels, so with --full the last step's results are compared against
+an oracle fingerprint committed under tests/golden/ (make_bench_fingerprint.py):
 ``check_vs_oracle``.  Prints ONE JSON line on rank 0.
 
-    python bench.py                      # N=1, default steps
+A plain run does what the headline needs and no more: set-up, warm-up, the
+timed steps (per-kernel event timing rides on them), the line.  --full adds
+the CPU baseline, the extras, the box probe, the oracle check and, at N > 1,
+the single-GPU run of the same workload and the isolated collectives.
+--dump-outputs DIR writes what the last timed step computed (dump_outputs).
+
+    python bench.py                      # N=1, default steps, the headline alone
+    python bench.py --full               # ... and every other measurement and check
     python bench.py --gpus N             # starts N rank processes itself (launch())
     torchrun --nproc-per-node N bench.py --gpus N
     python bench.py --gpus 1 --channels 4 --layout sharded   # configs[2]'s workload on 1 GPU
@@ -198,7 +205,25 @@ def parse():
                    help="PMC-derived HBM bytes per launch (written by tools/pmc_traffic.py; "
                         "default profiles/pmc_traffic.json, profiles/pmc_traffic_bright.json for "
                         "--distribution bright)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything beside the headline: the CPU "
+                        "baseline, the extras (one job at a time, chain pass, host path, input "
+                        "path), the box probe, the last step against the oracle fingerprints "
+                        "(check, check_vs_oracle) and, at N > 1, the single-GPU run of the same "
+                        "workload and the isolated collectives.  Without it a run sets up, "
+                        "warms up, times the steps and prints the line; --cpu-sample, "
+                        "--no-extras, --no-box and --no-same-workload narrow a --full run")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step's job computed "
+                        "to DIR/<name>.npy (float64 statistics, float32 corrected pixels; see "
+                        "dump_outputs): the same arguments give the same inputs, so two builds "
+                        "can be compared array for array")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:  # a plain run: nothing beside the headline
+        a.cpu_sample = 0
+        a.no_extras = a.no_box = a.no_same_workload = True
     if a.traffic_json is None:
         a.traffic_json = os.path.join(REPO, "profiles", "pmc_traffic%s.json" % (
             "" if a.distribution == "synthetic" else "_" + a.distribution))
@@ -944,6 +969,72 @@ def check_against_fingerprint(fp, res, smean, sstd, corr_sites):
         cnt += [np.count_nonzero(d == 0), np.count_nonzero(d == 1), np.count_nonzero(d == -1),
                 np.count_nonzero((np.abs(d) > 1) & ~flips), np.count_nonzero(flips)]
     return out, cnt
+
+
+# ---------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------
+
+DUMP_BYTES = 60 * 10 ** 6  # of all the files of one run together (under 64 MB)
+DUMP_SITES = 16            # corrected sites sampled per channel
+
+
+def dump_sample(npx, n_sites, n_channels, only_sites=None):
+    """The fixed sample of --dump-outputs, from SEED and the job's geometry
+    alone: (pixels of the statistics planes, local sites of the corrected
+    output, pixels of each of those sites), all sorted.  Everything is kept
+    where it fits: per channel a third of the budget goes to the four float64
+    planes, the rest to the float32 corrected pixels.  only_sites: the local
+    sites that may be sampled (default: all; the first and last always are)."""
+    rng = np.random.default_rng(SEED)
+    budget = DUMP_BYTES // n_channels - (100000 + 65536) * 8  # percentile sums, histogram
+    n_plane = min(npx, budget // 3 // (4 * 8))
+    plane_px = np.sort(rng.choice(npx, n_plane, replace=False))
+    if only_sites is not None:
+        sites = np.array(sorted(only_sites), dtype=np.int64)
+    elif n_sites <= DUMP_SITES:
+        sites = np.arange(n_sites, dtype=np.int64)
+    else:
+        sites = np.unique(np.concatenate([[0, n_sites - 1],
+                                          rng.choice(n_sites, DUMP_SITES - 2, replace=False)]))
+    n_site = min(npx, budget * 2 // 3 // (max(len(sites), 1) * 4))
+    site_px = np.sort(rng.choice(npx, n_site, replace=False))
+    return plane_px, sites, site_px
+
+
+def dump_outputs(path, L, torch, dev, jobs, site_of, n_sites, only_sites=None):
+    """What a caller of the timed path holds after the last timed step, as
+    path/<name>.npy (with several channels, channel c's names start with
+    ``c<c>_``): mean, std, smoothed_mean, smoothed_std (float64, the pixels
+    dump_sample picks, in index order), percentile_sums (float64, 100,000),
+    histogram (the pooled 65,536-bin counts as float64, exact) and corrected
+    (float32 [sites, pixels]: the sampled pixels of the sampled sites of this
+    rank's corrected output).  jobs: the channel jobs of the last timed step;
+    site_of(c, i): channel c's corrected local site i as a device tensor."""
+    from tmlibrary_amd import hip
+    os.makedirs(path, exist_ok=True)
+    npx = jobs[0].mean.numel()
+    plane_px, sites, site_px = dump_sample(npx, n_sites, len(jobs), only_sites)
+    plane_t = torch.from_numpy(plane_px).to(dev)
+    site_t = torch.from_numpy(site_px).to(dev)
+    torch.cuda.synchronize(dev)
+    for c, ch in enumerate(jobs):
+        mean, std = np.empty(npx), np.empty(npx)
+        acc, hist = np.empty(100000), np.empty(65536, np.uint64)
+        nn = C.c_int64()
+        hip.check(L.tmh_stats_finalize(ch.h, C.byref(nn), hip.ptr(mean), hip.ptr(std),
+                                       hip.ptr(acc), hip.ptr(hist)))
+        out = {"mean": mean[plane_px], "std": std[plane_px],
+               "smoothed_mean": ch.smean[plane_t].cpu().numpy(),
+               "smoothed_std": ch.sstd[plane_t].cpu().numpy(),
+               "percentile_sums": acc, "histogram": hist.astype(np.float64)}
+        corr = np.empty((len(sites), len(site_px)), np.float32)
+        for k, i in enumerate(sites.tolist()):
+            corr[k] = site_of(c, i).reshape(-1)[site_t].cpu().numpy().view(np.uint16)
+        out["corrected"] = corr
+        for name, arr in out.items():
+            np.save(os.path.join(path, "%s%s.npy" % ("c%d_" % c if len(jobs) > 1 else "", name)),
+                    arr)
 
 
 # ---------------------------------------------------------------------------
@@ -2002,8 +2093,16 @@ def main():
     if deep:  # the jobs in flight completed (untimed) before the checks
         deep_drain()
         torch.cuda.synchronize(dev)
+    if a.dump_outputs and rank == 0:
+        # the job of the last timed step (deep order: the job the drain completed)
+        last = ([lanes[(jobs["k"] - 1) % J]] if J > 1 else
+                sets[jobs["p"] % CJ] if deep else sets[(jobs["k"] - 1) % CJ])
+        log("writing the last step's outputs to %s" % a.dump_outputs)
+        dump_outputs(a.dump_outputs, L, torch, dev, last,
+                     lambda c, i: local_site(c, i, outputs=True), S,
+                     only_sites=checked if share_out else None)
     collectives = None
-    if dist_on and prof:  # one more step with every collective timed on its own
+    if dist_on and prof and a.full:  # one more step with every collective timed on its own
         ct = CollectiveTimer(torch, dev)
         for ch in chans:
             ch.stats()
@@ -2037,11 +2136,12 @@ def main():
                              "pct_chain_hist_allreduce_ms": round(float(np.mean(m)), 4)})
 
     # every channel's results after the last step (identical on every rank)
-    # against its oracle fingerprint (tests/golden/make_bench_fingerprint.py)
+    # against its oracle fingerprint (tests/golden/make_bench_fingerprint.py);
+    # a plain run checks nothing (check stays empty, check_vs_oracle null)
     check, check_ok = {}, None
     per_channel = {}
     for c, ch in (list(enumerate(chans)) + [(0, ln) for ln in lanes[len(chans):]] +
-                  [(c, ch) for X in sets[1:] for c, ch in enumerate(X)]):
+                  [(c, ch) for X in sets[1:] for c, ch in enumerate(X)]) if a.full else ():
         nn = C.c_int64()
         res = {"mean": np.empty(npx), "std": np.empty(npx), "acc": np.empty(Q),
                "hist": np.empty(65536, np.uint64)}
@@ -2245,6 +2345,7 @@ def main():
             "ranks": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "ms_per_step": round(1e3 * elapsed / a.steps, 3),
             "host_queue_ms_per_step": [round(float(np.median(host_ms)), 3),
                                        round(float(np.max(host_ms)), 3)],

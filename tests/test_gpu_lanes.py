@@ -49,7 +49,7 @@ def test_bench_two_lanes():
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--sites", "48", "--steps",
-                        "3", "--warmup", "1", "--no-extras", "--cpu-sample", "0"],
+                        "3", "--warmup", "1", "--full", "--no-extras", "--cpu-sample", "0"],
                        cwd=REPO, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        timeout=540)
     assert r.returncode == 0, r.stderr.decode()[-4000:]

@@ -33,7 +33,7 @@ pytestmark = pytest.mark.gpu
 
 BENCH = os.path.join(REPO, "bench.py")
 ARGS = ["--layout", "sharded", "--channels", "4", "--sites", "48", "--steps", "2", "--warmup",
-        "1", "--no-extras", "--cpu-sample", "0", "--no-same-workload"]
+        "1", "--full", "--no-extras", "--cpu-sample", "0", "--no-same-workload"]
 
 
 def _port():

@@ -11,8 +11,9 @@
 #                  when libhdf5 is there) from the pushed sources, toolchain
 #                  and sha256 logged (build_TAG.log)
 #   tests          pytest -m gpu, then smoke (gpu_tests_TAG.log, smoke_TAG.log)
-#   bench          the default bench line, CPU baseline included (bench_TAG.json)
-#   quick          bench --steps 10 --no-extras --cpu-sample 0 (bench_quick_TAG.json)
+#   bench          the bench --full line, CPU baseline included (bench_TAG.json)
+#   quick          bench --full --steps 10 --no-extras --cpu-sample 0: the headline,
+#                  the oracle check and the box probe (bench_quick_TAG.json)
 #   bright         quick on bright data (bench_bright_TAG.json)
 #   repeat:N       N more quick bench processes (bench_repeat_TAG.jsonl)
 #   dist432        one rank, forced-distributed, 4 channels x 432 sites: each
@@ -37,10 +38,10 @@ shift
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 O=gpurun_out
-QB="bench.py --steps 10 --warmup 3 --cpu-sample 0 --no-extras ${BENCH_ARGS:-}"
+QB="bench.py --full --steps 10 --warmup 3 --cpu-sample 0 --no-extras ${BENCH_ARGS:-}"
 # (the profiled bench keeps its own event timing: its line and the rocprof
 # summary then describe the same process)
-SB="bench.py --steps 5 --warmup 2 --cpu-sample 0 --no-extras ${BENCH_ARGS:-}"
+SB="bench.py --full --steps 5 --warmup 2 --cpu-sample 0 --no-extras ${BENCH_ARGS:-}"
 
 summ() {  # one-line summary of a bench JSON line
   python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.strip()][-1]); r=d.get('roofline') or {}; print(sys.argv[1], d['value'], d['ms_per_step'], d.get('check_vs_oracle'), r.get('frac'), {k: v['avg_ms'] for k, v in d.get('kernels', {}).items()})" "$1"
@@ -71,7 +72,7 @@ for step in "$@"; do
       if [ $rc -ne 0 ]; then exit $rc; fi
       ;;
     bench)
-      timeout -k 10 900 python bench.py > $O/bench_$TAG.json 2> $O/bench_$TAG.err || exit $?
+      timeout -k 10 900 python bench.py --full > $O/bench_$TAG.json 2> $O/bench_$TAG.err || exit $?
       summ $O/bench_$TAG.json
       ;;
     quick)
@@ -92,7 +93,7 @@ for step in "$@"; do
       ;;
     dist432)
       TMH_BENCH_FORCE_DIST=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 \
-        timeout -k 10 300 python bench.py --layout sharded --channels 4 --sites 432 --steps 10 \
+        timeout -k 10 300 python bench.py --full --layout sharded --channels 4 --sites 432 --steps 10 \
         --warmup 3 --no-extras --cpu-sample 0 ${BENCH_ARGS:-} > $O/dist432_$TAG.json 2> $O/dist432_$TAG.err || exit $?
       summ $O/dist432_$TAG.json
       ;;
@@ -100,7 +101,7 @@ for step in "$@"; do
       # one variant: dist432v:--flag+value+--flag2 ('+' for spaces), appended to dist432_v_TAG.jsonl
       V=$(echo "$a1" | tr '+' ' ')
       TMH_BENCH_FORCE_DIST=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 \
-        timeout -k 10 300 python bench.py --layout sharded --channels 4 --sites 432 --steps 10 \
+        timeout -k 10 300 python bench.py --full --layout sharded --channels 4 --sites 432 --steps 10 \
         --warmup 3 --no-extras --cpu-sample 0 ${BENCH_ARGS:-} $V > $O/dist432v.tmp 2>> $O/dist432_v_$TAG.err || exit $?
       python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.strip()][-1]); print(json.dumps({'variant': sys.argv[2], 'value': d['value'], 'ms': d['ms_per_step'], 'host_ms': d.get('host_queue_ms_per_step'), 'check': d['check_vs_oracle'], 'k': {k: v['avg_ms'] for k, v in d['kernels'].items()}}))" $O/dist432v.tmp "$V" | tee -a $O/dist432_v_$TAG.jsonl
       ;;
@@ -116,7 +117,7 @@ for step in "$@"; do
         for L in "${ORDER[@]}"; do
           IFS=+ read -r -a LA <<< "$L"
           TMH_LIB=${LA[0]} TMH_BENCH_FORCE_DIST=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 \
-            MASTER_PORT=29517 timeout -k 10 300 python bench.py --layout sharded --channels 4 --sites 432 \
+            MASTER_PORT=29517 timeout -k 10 300 python bench.py --full --layout sharded --channels 4 --sites 432 \
             --steps 10 --warmup 3 --no-extras --cpu-sample 0 "${LA[@]:1}" > $O/ab432_$TAG.tmp 2>> $O/ab432_$TAG.err || exit $?
           python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[2]) if l.strip()][-1]); print(json.dumps({'lib': sys.argv[1], 'value': d['value'], 'ms': d['ms_per_step'], 'check': d['check_vs_oracle'], 'k': {k: v['avg_ms'] for k, v in d['kernels'].items()}}))" "$L" $O/ab432_$TAG.tmp >> $O/ab432_$TAG.jsonl
           tail -1 $O/ab432_$TAG.jsonl
@@ -126,7 +127,7 @@ for step in "$@"; do
     prof432)
       TMH_BENCH_FORCE_DIST=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 \
         timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_dist432_$TAG -o run \
-        -- python3 bench.py --layout sharded --channels 4 --sites 432 --steps 5 --warmup 2 \
+        -- python3 bench.py --full --layout sharded --channels 4 --sites 432 --steps 5 --warmup 2 \
         --no-extras --cpu-sample 0 ${BENCH_ARGS:-} > $O/rocprof_dist432_$TAG.json 2> $O/rocprof_dist432_$TAG.log || exit $?
       summ $O/rocprof_dist432_$TAG.json
       ;;
@@ -137,7 +138,7 @@ for step in "$@"; do
       TMH_BENCH_FORCE_DIST=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 \
         timeout -k 10 300 rocprofv3 --kernel-trace --hip-runtime-trace --memory-copy-trace \
         --output-format csv -d $O/rocprof_dist432h_$TAG -o run \
-        -- python3 bench.py --layout sharded --channels 4 --sites 432 --steps 5 --warmup 2 \
+        -- python3 bench.py --full --layout sharded --channels 4 --sites 432 --steps 5 --warmup 2 \
         --no-extras --cpu-sample 0 ${BENCH_ARGS:-} $V > $O/rocprof_dist432h_$TAG.json 2> $O/rocprof_dist432h_$TAG.log || exit $?
       summ $O/rocprof_dist432h_$TAG.json
       ;;
@@ -179,7 +180,7 @@ for step in "$@"; do
       D=${a1:-synthetic}
       for c in FETCH_SIZE WRITE_SIZE; do
         timeout -s KILL 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_${c}_${D}_$TAG -o run \
-          -- python3 bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-extras --no-profile --distribution $D \
+          -- python3 bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-extras --no-profile --distribution $D \
           > $O/pmc_${c}_${D}_$TAG.log 2>&1 || exit $?
       done
       python3 tools/pmc_traffic.py $O/pmc_FETCH_SIZE_${D}_$TAG $O/pmc_WRITE_SIZE_${D}_$TAG --sites 3456 \
@@ -207,7 +208,7 @@ for step in "$@"; do
       for P in "$PA" "$PB"; do
         n=$((n + 1))
         timeout -s KILL 240 rocprofv3 --pmc $P --kernel-trace --output-format csv -d $O/pmcsq${n}_${D}_$TAG -o run \
-          -- python3 bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-extras --no-profile --no-box \
+          -- python3 bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-extras --no-profile --no-box \
           --jobs-in-flight 1 --distribution $D > $O/pmcsq${n}_${D}_$TAG.log 2>&1 || exit $?
       done
       python3 tools/pmc_sq.py $O/pmcsq1_${D}_$TAG $O/pmcsq2_${D}_$TAG --pixels $((3456 * 2160 * 2560)) \
@@ -247,7 +248,7 @@ for step in "$@"; do
       case $name in
         abenv) CMD="python $QB"; DE="" ;;
         abenvb) CMD="python $QB --distribution bright"; DE="" ;;
-        abenv432) CMD="python bench.py --layout sharded --channels 4 --sites 432 --steps 10 --warmup 3 --no-extras --cpu-sample 0 ${BENCH_ARGS:-}"
+        abenv432) CMD="python bench.py --full --layout sharded --channels 4 --sites 432 --steps 10 --warmup 3 --no-extras --cpu-sample 0 ${BENCH_ARGS:-}"
           DE="TMH_BENCH_FORCE_DIST=1 WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517" ;;
       esac
       for i in $(seq 1 ${a1:-3}); do
