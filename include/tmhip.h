@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TMH_ABI_VERSION 4
+#define TMH_ABI_VERSION 5
 
 #define TMH_OK 0
 #define TMH_EINVAL (-22)  /* bad argument: maps to ValueError / TypeError */
@@ -422,6 +422,59 @@ int tmh_correct_chain_u8_device(tmh_corrector* c, const uint16_t* dev_in, uint8_
 int tmh_correct_chain_u8(tmh_corrector* c, const uint16_t* host_in, uint8_t* host_out,
                          int64_t n_sites, const tmh_window* host_windows, int clip_lo,
                          int clip_hi);
+
+/* ---- illuminati tile pyramid ------------------------------------------------
+ * Replaces the pixel work of tmlib/workflow/illuminati/api.py:356-501
+ * (_create_maxzoom_level_tiles: every site stitched into 256 x 256 base tiles,
+ * with pixels of the upper and left neighbours) and :503-573
+ * (_create_lower_zoom_level_tiles: 2 x 2 tile mosaic -> Image.shrink).
+ * Tile-major storage: a level is [tile_rows][tile_cols][256][256] uint8, each
+ * tile 64 KB contiguous; a ragged tile (last row / column of a level) lies in
+ * its tile's top left corner at the 256-byte row pitch, zeros around it.
+ *
+ * One rectangle of the base gather: tile `tile` (row-major index) takes
+ * height x width bytes of site `site` from (src_y, src_x) at (dst_y, dst_x).
+ * The host evaluates the reference's extract / pad / insert rules into the
+ * table (tmlibrary_amd/workflow/pyramid.py); rectangles of one tile must be
+ * disjoint (which of two overlapping ones a byte takes is unspecified). */
+typedef struct tmh_tile_rect {
+  int32_t tile, site, src_y, src_x, dst_y, dst_x, height, width;
+} tmh_tile_rect;
+/* Gather host_rects[n_rects] (any order) from dev_sites [n_sites][height][width]
+ * uint8 (tmh_correct_chain_u8_device's output) into dev_tiles
+ * [tile_rows][tile_cols][256][256]: every byte of every tile is written once,
+ * 0 where no rectangle covers it (spacer tiles are all 0: what api.py:550
+ * substitutes for a missing base tile).  dev_tiles 16-byte aligned.  The
+ * table is checked first (a rectangle leaving its site or tile, an index out
+ * of range, a non-positive size: TMH_EINVAL, nothing launched), then uploaded
+ * and the gather queued on `stream` (NULL: the default stream); the call
+ * returns once the gather has run (it frees the uploaded table), so
+ * host_rects may be reused at once. */
+int tmh_tiles_base_device(const uint8_t* dev_sites, int64_t n_sites, int height, int width,
+                          const tmh_tile_rect* host_rects, int64_t n_rects, uint8_t* dev_tiles,
+                          int tile_rows, int tile_cols, void* stream);
+int tmh_tiles_base(const uint8_t* host_sites, int64_t n_sites, int height, int width,
+                   const tmh_tile_rect* host_rects, int64_t n_rects, uint8_t* host_tiles,
+                   int tile_rows, int tile_cols);
+/* One level to the next: output tile (y, x) of the ceil(src_rows / 2) x
+ * ceil(src_cols / 2) output level is the mosaic of source tiles (2y..2y+1,
+ * 2x..2x+1) that exist, halved with (a + b + c + d + 2) >> 2 per pixel
+ * (OpenCV's integer INTER_AREA path at scale 2 on uint8, which Image.shrink,
+ * image.py:313-343, reaches through cv2.resize).  Only the last tile row /
+ * column of a level may be smaller than 256: src_last_h / src_last_w (1..256)
+ * give theirs, *dst_last_h / *dst_last_w report the output level's (half the
+ * last mosaic's side, rounded down; TMH_EINVAL if that is 0).  A mosaic with
+ * an odd side has no scale-2 path: its output tile is NOT written (the caller
+ * computes it, pyramid.py's exact area mean); every other output tile is
+ * written whole, zeros outside its ragged extent.  Both levels 16-byte
+ * aligned and distinct.  Asynchronous on `stream` (NULL: the default
+ * stream); the host form is synchronous and keeps host_dst's bytes in the
+ * tiles it does not write. */
+int tmh_pyramid_shrink2_device(const uint8_t* dev_src, int src_rows, int src_cols, int src_last_h,
+                               int src_last_w, uint8_t* dev_dst, int* dst_last_h, int* dst_last_w,
+                               void* stream);
+int tmh_pyramid_shrink2(const uint8_t* host_src, int src_rows, int src_cols, int src_last_h,
+                        int src_last_w, uint8_t* host_dst, int* dst_last_h, int* dst_last_w);
 
 /* ChannelImage.clip alone (image.py:589), u16. */
 int tmh_clip_u16(const uint16_t* host_in, uint16_t* host_out, int64_t n, int lo, int hi);

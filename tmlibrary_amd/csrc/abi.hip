@@ -2098,6 +2098,144 @@ int tmh_correct_chain_u8(tmh_corrector* c, const uint16_t* host_in, uint8_t* hos
   });
 }
 
+// ---------------------------------------------------------------------------
+// illuminati tile pyramid
+// ---------------------------------------------------------------------------
+
+static constexpr int kPyrTile = 256;
+
+static void check_tile_rects(const tmh_tile_rect* r, int64_t n, int64_t n_sites, int H, int W,
+                             int64_t n_tiles) {
+  for (int64_t i = 0; i < n; ++i) {
+    const tmh_tile_rect& q = r[i];
+    TMH_CHECK(q.tile >= 0 && q.tile < n_tiles, TMH_EINVAL, "tile index out of range");
+    TMH_CHECK(q.site >= 0 && q.site < n_sites, TMH_EINVAL, "site index out of range");
+    TMH_CHECK(q.height > 0 && q.width > 0, TMH_EINVAL, "rectangle has a non-positive size");
+    TMH_CHECK(q.src_y >= 0 && q.src_x >= 0 && (int64_t)q.src_y + q.height <= H &&
+                  (int64_t)q.src_x + q.width <= W,
+              TMH_EINVAL, "rectangle leaves its site");
+    TMH_CHECK(q.dst_y >= 0 && q.dst_x >= 0 && (int64_t)q.dst_y + q.height <= kPyrTile &&
+                  (int64_t)q.dst_x + q.width <= kPyrTile,
+              TMH_EINVAL, "rectangle leaves its tile");
+  }
+}
+
+static void check_tiles_args(const void* sites, int64_t n_sites, int height, int width,
+                             const tmh_tile_rect* rects, int64_t n_rects, const void* tiles,
+                             int tile_rows, int tile_cols) {
+  TMH_CHECK(sites && tiles, TMH_EINVAL, "sites or tiles pointer is NULL");
+  TMH_CHECK(rects || n_rects == 0, TMH_EINVAL, "rectangle table is NULL");
+  TMH_CHECK(n_sites > 0 && height > 0 && width > 0 && tile_rows > 0 && tile_cols > 0 &&
+                n_rects >= 0,
+            TMH_EINVAL, "sizes must be positive");
+  TMH_CHECK((int64_t)tile_rows * tile_cols < (int64_t(1) << 31) && n_rects < (int64_t(1) << 31),
+            TMH_EINVAL, "more than 2^31 tiles or rectangles");
+  check_tile_rects(rects, n_rects, n_sites, height, width, (int64_t)tile_rows * tile_cols);
+}
+
+int tmh_tiles_base_device(const uint8_t* dev_sites, int64_t n_sites, int height, int width,
+                          const tmh_tile_rect* host_rects, int64_t n_rects, uint8_t* dev_tiles,
+                          int tile_rows, int tile_cols, void* stream) {
+  return guard([&] {
+    check_tiles_args(dev_sites, n_sites, height, width, host_rects, n_rects, dev_tiles, tile_rows,
+                     tile_cols);
+    TMH_CHECK((reinterpret_cast<uintptr_t>(dev_tiles) & 15) == 0, TMH_EINVAL,
+              "tiles must be 16-byte aligned");
+    const int64_t nt = (int64_t)tile_rows * tile_cols;
+    // counting sort by tile: tbeg[t] .. tbeg[t + 1] index tile t's rectangles
+    std::vector<int> tbeg((size_t)nt + 1, 0);
+    for (int64_t i = 0; i < n_rects; ++i) tbeg[(size_t)host_rects[i].tile + 1] += 1;
+    for (int64_t t = 0; t < nt; ++t) tbeg[(size_t)t + 1] += tbeg[(size_t)t];
+    std::vector<tmh_tile_rect> sorted((size_t)std::max<int64_t>(n_rects, 1));
+    {
+      std::vector<int> at(tbeg.begin(), tbeg.end() - 1);
+      for (int64_t i = 0; i < n_rects; ++i) sorted[(size_t)at[(size_t)host_rects[i].tile]++] = host_rects[i];
+    }
+    DBuf<tmh_tile_rect> d_rects;
+    DBuf<int> d_tbeg;
+    d_rects.alloc(sorted.size());
+    d_tbeg.alloc(tbeg.size());
+    const hipStream_t s = (hipStream_t)stream;
+    TMH_HIP(hipMemcpyAsync(d_rects.p, sorted.data(), sorted.size() * sizeof(tmh_tile_rect),
+                           hipMemcpyHostToDevice, s));
+    TMH_HIP(hipMemcpyAsync(d_tbeg.p, tbeg.data(), tbeg.size() * sizeof(int), hipMemcpyHostToDevice,
+                           s));
+    launch_tiles_base(dev_sites, n_sites, height, width, d_rects.p, d_tbeg.p, dev_tiles, nt, s);
+    TMH_HIP(hipStreamSynchronize(s));  // the table's buffers are freed on return
+  });
+}
+
+int tmh_tiles_base(const uint8_t* host_sites, int64_t n_sites, int height, int width,
+                   const tmh_tile_rect* host_rects, int64_t n_rects, uint8_t* host_tiles,
+                   int tile_rows, int tile_cols) {
+  return guard([&] {
+    check_tiles_args(host_sites, n_sites, height, width, host_rects, n_rects, host_tiles,
+                     tile_rows, tile_cols);
+    const size_t in_b = (size_t)n_sites * height * width;
+    const size_t out_b = (size_t)tile_rows * tile_cols * kPyrTile * kPyrTile;
+    DBuf<uint8_t> a, b;
+    a.alloc(in_b);
+    b.alloc(out_b);
+    TMH_HIP(hipMemcpy(a.p, host_sites, in_b, hipMemcpyHostToDevice));
+    int rc = tmh_tiles_base_device(a.p, n_sites, height, width, host_rects, n_rects, b.p,
+                                   tile_rows, tile_cols, nullptr);
+    if (rc) throw Error{rc, g_last_error};
+    TMH_HIP(hipMemcpy(host_tiles, b.p, out_b, hipMemcpyDeviceToHost));
+  });
+}
+
+// side of the last output mosaic along an axis of n source tiles
+static int last_mosaic_side(int n, int last) {
+  return (n & 1) ? last : kPyrTile + last;
+}
+
+static void check_shrink_args(const void* src, int rows, int cols, int last_h, int last_w,
+                              const void* dst, const int* dlh, const int* dlw) {
+  TMH_CHECK(src && dst && dlh && dlw, TMH_EINVAL, "NULL pointer");
+  TMH_CHECK(rows > 0 && cols > 0, TMH_EINVAL, "sizes must be positive");
+  TMH_CHECK(last_h >= 1 && last_h <= kPyrTile && last_w >= 1 && last_w <= kPyrTile, TMH_EINVAL,
+            "last tile row height / column width must be in 1..256");
+  TMH_CHECK(last_mosaic_side(rows, last_h) >= 2 && last_mosaic_side(cols, last_w) >= 2, TMH_EINVAL,
+            "a last mosaic one pixel wide has no half");
+  TMH_CHECK(src != dst, TMH_EINVAL, "source and output level must be distinct");
+}
+
+int tmh_pyramid_shrink2_device(const uint8_t* dev_src, int src_rows, int src_cols, int src_last_h,
+                               int src_last_w, uint8_t* dev_dst, int* dst_last_h, int* dst_last_w,
+                               void* stream) {
+  return guard([&] {
+    check_shrink_args(dev_src, src_rows, src_cols, src_last_h, src_last_w, dev_dst, dst_last_h,
+                      dst_last_w);
+    TMH_CHECK(((reinterpret_cast<uintptr_t>(dev_src) | reinterpret_cast<uintptr_t>(dev_dst)) & 15) == 0,
+              TMH_EINVAL, "levels must be 16-byte aligned");
+    launch_pyramid_shrink2(dev_src, src_rows, src_cols, src_last_h, src_last_w, dev_dst,
+                           (hipStream_t)stream);
+    *dst_last_h = last_mosaic_side(src_rows, src_last_h) / 2;
+    *dst_last_w = last_mosaic_side(src_cols, src_last_w) / 2;
+  });
+}
+
+int tmh_pyramid_shrink2(const uint8_t* host_src, int src_rows, int src_cols, int src_last_h,
+                        int src_last_w, uint8_t* host_dst, int* dst_last_h, int* dst_last_w) {
+  return guard([&] {
+    check_shrink_args(host_src, src_rows, src_cols, src_last_h, src_last_w, host_dst, dst_last_h,
+                      dst_last_w);
+    const size_t tb = (size_t)kPyrTile * kPyrTile;
+    const size_t in_b = (size_t)src_rows * src_cols * tb;
+    const size_t out_b = (size_t)((src_rows + 1) / 2) * ((src_cols + 1) / 2) * tb;
+    DBuf<uint8_t> a, b;
+    a.alloc(in_b);
+    b.alloc(out_b);
+    TMH_HIP(hipMemcpy(a.p, host_src, in_b, hipMemcpyHostToDevice));
+    TMH_HIP(hipMemcpy(b.p, host_dst, out_b, hipMemcpyHostToDevice));  // odd mosaics keep theirs
+    int rc = tmh_pyramid_shrink2_device(a.p, src_rows, src_cols, src_last_h, src_last_w, b.p,
+                                        dst_last_h, dst_last_w, nullptr);
+    if (rc) throw Error{rc, g_last_error};
+    TMH_HIP(hipStreamSynchronize(nullptr));
+    TMH_HIP(hipMemcpy(host_dst, b.p, out_b, hipMemcpyDeviceToHost));
+  });
+}
+
 int tmh_clip_u16(const uint16_t* host_in, uint16_t* host_out, int64_t n, int lo, int hi) {
   return guard([&] {
     TMH_CHECK((host_in && host_out) || n == 0, TMH_EINVAL, "bad arguments");

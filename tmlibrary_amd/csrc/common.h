@@ -441,6 +441,13 @@ void launch_inflate(const uint8_t* src, int64_t src_bytes, const tmh_zchunk* chu
 void launch_place_chunks(const uint8_t* raw, const tmh_zchunk* chunks, int64_t n_chunks,
                          int height, int width, int esize, int chunk_rows, int chunk_cols,
                          uint8_t* images, hipStream_t s);
+// illuminati tile pyramid (pyramid_kernels.hip); d_tbeg[n_tiles + 1]: tile t's
+// rectangles are d_rects[d_tbeg[t], d_tbeg[t + 1])
+void launch_tiles_base(const uint8_t* sites, int64_t n_sites, int H, int W,
+                       const tmh_tile_rect* d_rects, const int* d_tbeg, uint8_t* tiles,
+                       int64_t n_tiles, hipStream_t s);
+void launch_pyramid_shrink2(const uint8_t* src, int R, int C, int last_h, int last_w, uint8_t* dst,
+                            hipStream_t s);
 void launch_clip_u16(const uint16_t* in, uint16_t* out, int64_t n, int lo, int hi, hipStream_t s);
 void launch_synth(uint16_t* out, int64_t n_sites, int H, int W, uint64_t seed, int channel,
                   int64_t first_site, int dist, hipStream_t s);

@@ -33,7 +33,7 @@ TMH_FUSED_NO_HIST = 100
 TMH_SYNTH_STANDARD = 0
 TMH_SYNTH_BRIGHT = 1
 TMH_SYNTH_UNIFORM = 2
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _P = C.c_void_p
 _I64 = C.c_int64
@@ -100,6 +100,10 @@ SIGNATURES = {
     "tmh_map_u16_to_u8": (_I, [_P, _P, _I64, _I, _I]),
     "tmh_correct_chain_u8_device": (_I, [_P, _P, _P, _I64, _P, _I, _I, _P]),
     "tmh_correct_chain_u8": (_I, [_P, _P, _P, _I64, _P, _I, _I]),
+    "tmh_tiles_base_device": (_I, [_P, _I64, _I, _I, _P, _I64, _P, _I, _I, _P]),
+    "tmh_tiles_base": (_I, [_P, _I64, _I, _I, _P, _I64, _P, _I, _I]),
+    "tmh_pyramid_shrink2_device": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(_I), C.POINTER(_I), _P]),
+    "tmh_pyramid_shrink2": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(_I), C.POINTER(_I)]),
     "tmh_synth_sites_device": (_I, [_P, _I64, _I, _I, C.c_uint64, _I, _I64, _I, _P]),
     "tmh_synth_tables": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "tmh_box_probe_device": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I, _P, C.POINTER(_D),
@@ -119,6 +123,12 @@ SIGNATURES = {
 #: struct tmh_window (include/tmhip.h) as a numpy record: one alignment window per site
 WINDOW_DTYPE = np.dtype([("src_r0", np.int32), ("src_c0", np.int32), ("dst_r0", np.int32),
                          ("dst_c0", np.int32), ("rows", np.int32), ("cols", np.int32)])
+
+
+#: struct tmh_tile_rect (include/tmhip.h): one rectangle of the base-tile gather
+TILE_RECT_DTYPE = np.dtype([(k, np.int32) for k in ("tile", "site", "src_y", "src_x", "dst_y",
+                                                    "dst_x", "height", "width")])
+assert TILE_RECT_DTYPE.itemsize == 32
 
 
 #: struct tmh_zchunk (include/tmhip.h): one HDF5 gzip chunk of the input path

@@ -24,7 +24,7 @@ import ctypes as C
 import numpy as np
 
 from . import hip
-from .metadata import ImageMetadata, IllumstatsImageMetadata
+from .metadata import ImageMetadata, IllumstatsImageMetadata, PyramidTileMetadata
 
 #: np.log10(1e-10) on this host: the log of a zero pixel in the correction
 #: (image.py:624-626 replaces 0 by 10**-10 before the log10)
@@ -107,6 +107,105 @@ class Image(object):
         new_object.metadata.is_aligned = True
         return new_object
 
+    def extract(self, y_offset, height, x_offset, width):
+        """image.py:131-153: the rectangle [y_offset : y_offset + height,
+        x_offset : x_offset + width] (numpy slicing: clipped at the edge; a
+        view, as in the reference)."""
+        array = self.array[y_offset:(y_offset + height), x_offset:(x_offset + width)]
+        return self.__class__(array, self.metadata)
+
+    def insert(self, image, y_offset, x_offset, inplace=True):
+        """image.py:155-189: write ``image``'s pixels at (y_offset, x_offset)."""
+        if not isinstance(image, Image):
+            raise TypeError('Argument "image" must have type tmlib.image.Image.')
+        if (image.dimensions[0] + y_offset > self.dimensions[0] or
+                image.dimensions[1] + x_offset > self.dimensions[1]):
+            raise ValueError('Image doesn\'t fit.')
+        if inplace:
+            array = self.array
+        else:
+            array = self.array.copy()
+        height, width = image.dimensions
+        array[y_offset:(y_offset + height), x_offset:(x_offset + width)] = image.array
+        if inplace:
+            return self
+        return self.__class__(array, self.metadata)
+
+    def merge(self, image, axis, offset, inplace=True):
+        """image.py:191-226: take ``image``'s pixels from ``offset`` on along
+        ``axis`` ('y' or 'x')."""
+        if not isinstance(image, Image):
+            raise TypeError('Argument "image" must have type tmlib.image.Image.')
+        if inplace:
+            array = self.array
+        else:
+            array = self.array.copy()
+        if axis == 'y':
+            array[offset:, :] = image.array[offset:, :]
+        elif axis == 'x':
+            array[:, offset:] = image.array[:, offset:]
+        else:
+            raise ValueError('Unknown axis.')
+        if inplace:
+            return self
+        return self.__class__(array, self.metadata)
+
+    def join(self, image, axis):
+        """image.py:228-251: stack ``image`` below ('y') or to the right ('x')."""
+        if not isinstance(image, Image):
+            raise TypeError('Argument "image" must have type tmlib.image.Image.')
+        if axis == 'y':
+            array = np.vstack([self.array, image.array])
+        elif axis == 'x':
+            array = np.hstack([self.array, image.array])
+        else:
+            raise ValueError('Unknown axis.')
+        return self.__class__(array, self.metadata)
+
+    def pad_with_background(self, n, side):
+        """image.py:253-285: ``n`` rows / columns of zeros on one side."""
+        height, width = self.dimensions
+        if side == 'top':
+            array = np.zeros((n, width), dtype=self.dtype)
+            array = np.vstack([array, self.array])
+        elif side == 'bottom':
+            array = np.zeros((n, width), dtype=self.dtype)
+            array = np.vstack([self.array, array])
+        elif side == 'left':
+            array = np.zeros((height, n), dtype=self.dtype)
+            array = np.hstack([array, self.array])
+        elif side == 'right':
+            array = np.zeros((height, n), dtype=self.dtype)
+            array = np.hstack([self.array, array])
+        else:
+            raise ValueError('Unknown side.')
+        return self.__class__(array, self.metadata)
+
+    def shrink(self, factor, inplace=True):
+        """image.py:313-343: shrink both axes by ``factor``, each output pixel
+        the mean of its neighbourhood (cv2.resize, INTER_AREA, to
+        (width / factor, height / factor) with Python 2's integer division).
+
+        Factor 2 on uint8 only (what the pyramid uses): even sides run on the
+        device, (a + b + c + d + 2) >> 2 per pixel (OpenCV's integer path at
+        scale 2); an array with an odd side has no such path and takes the
+        host's exact area mean over floor(side / 2) pixels, rounded half to
+        even (workflow/pyramid.py)."""
+        if factor != 2 or self.array.dtype != np.uint8:
+            raise NotImplementedError(
+                'Image.shrink supports factor 2 on uint8 arrays only '
+                '(got factor %r on %s).' % (factor, self.array.dtype))
+        height, width = self.dimensions
+        if height % 2 or width % 2:
+            from .workflow.pyramid import _area_mean_odd
+            array = _area_mean_odd(self.array)
+        else:
+            array = shrink2_array(self.array)
+        if inplace:
+            self.array = array
+            return self
+        return self.__class__(array, self.metadata)
+
     def smooth(self, sigma, inplace=True):
         """Gaussian smoothing (image.py:287-311 -> mahotas.gaussian_filter),
         'reflect' border, radius int(4*sigma+0.5), float64, on the GPU."""
@@ -163,6 +262,42 @@ def align_array(array: np.ndarray, window, out_shape) -> np.ndarray:
     hip.check(hip.lib().tmh_align(hip.ptr(a), hip.ptr(out), a.itemsize, 1, a.shape[0],
                                   a.shape[1], hip.ptr(win), out_shape[0], out_shape[1]))
     return out
+
+
+_TILE = 256
+
+
+def array_to_tiles(array: np.ndarray):
+    """An array cut into tile-major storage [rows][cols][256][256] (ragged
+    last row / column zero padded): (tiles, last row's height, last column's
+    width)."""
+    h, w = array.shape
+    rows, cols = -(-h // _TILE), -(-w // _TILE)
+    full = np.zeros((rows * _TILE, cols * _TILE), dtype=array.dtype)
+    full[:h, :w] = array
+    tiles = full.reshape(rows, _TILE, cols, _TILE).transpose(0, 2, 1, 3)
+    return np.ascontiguousarray(tiles), h - (rows - 1) * _TILE, w - (cols - 1) * _TILE
+
+
+def tiles_to_array(tiles: np.ndarray, last_h: int, last_w: int) -> np.ndarray:
+    """The inverse of ``array_to_tiles``."""
+    rows, cols = tiles.shape[:2]
+    full = tiles.transpose(0, 2, 1, 3).reshape(rows * _TILE, cols * _TILE)
+    return np.ascontiguousarray(full[:(rows - 1) * _TILE + last_h, :(cols - 1) * _TILE + last_w])
+
+
+def shrink2_array(array: np.ndarray) -> np.ndarray:
+    """A uint8 array with even sides halved on the device (tmh_pyramid_shrink2)."""
+    a = np.ascontiguousarray(array)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.shape[0] % 2 or a.shape[1] % 2 or a.size == 0:
+        raise ValueError("shrink2_array takes a non-empty uint8 array with even sides")
+    tiles, last_h, last_w = array_to_tiles(a)
+    rows, cols = tiles.shape[:2]
+    out = np.zeros(((rows + 1) // 2, (cols + 1) // 2, _TILE, _TILE), dtype=np.uint8)
+    oh, ow = C.c_int(), C.c_int()
+    hip.check(hip.lib().tmh_pyramid_shrink2(hip.ptr(tiles), rows, cols, last_h, last_w,
+                                            hip.ptr(out), C.byref(oh), C.byref(ow)))
+    return tiles_to_array(out, oh.value, ow.value)
 
 
 def smooth_f64(array: np.ndarray, sigma) -> np.ndarray:
@@ -376,6 +511,64 @@ class Corrector(object):
             self.close()
         except Exception:
             pass
+
+
+class PyramidTile(Image):
+    """A pyramid tile: uint8, at most 256 x 256 pixels (tmlib/image.py:927-1071;
+    the JPEG codec methods are not mirrored)."""
+
+    TILE_SIZE = 256
+
+    def __init__(self, array, metadata=None):
+        if metadata is not None and not isinstance(metadata, PyramidTileMetadata):
+            raise TypeError('Argument "metadata" must have type '
+                            'tmlib.metadata.PyramidTileMetadata.')
+        super(PyramidTile, self).__init__(array, metadata)
+        if not self.is_uint8:
+            raise TypeError('Image must have 8-bit unsigned integer data type.')
+        if any([d > self.TILE_SIZE or d == 0 for d in self.array.shape]):
+            raise ValueError('Height and width of image must be greater than zero and '
+                             'maximally %d pixels.' % self.TILE_SIZE)
+
+    @property
+    def metadata(self):
+        return self._metadata
+
+    @metadata.setter
+    def metadata(self, value):
+        if value is not None:
+            if not isinstance(value, PyramidTileMetadata):
+                raise TypeError('Argument "metadata" must have type '
+                                'tmlib.metadata.PyramidTileMetadata.')
+        self._metadata = value
+
+    @property
+    def array(self):
+        return self._array
+
+    @array.setter
+    def array(self, value):
+        if not isinstance(value, np.ndarray):
+            raise TypeError('Argument "array" must have type numpy.ndarray.')
+        if value.ndim != 2:
+            raise ValueError('Argument "array" must be two dimensional.')
+        if not value.dtype == np.uint8:
+            raise ValueError('Argument "array" must have numpy.uint8 data type.')
+        self._array = value
+
+    @classmethod
+    def create_as_background(cls, add_noise=False, mu=None, sigma=None, metadata=None):
+        """image.py:1039-1071: a tile of zeros.  (With ``add_noise`` the
+        reference builds a 1-D array its own constructor then rejects; the
+        missing-argument ``ValueError`` comes first and is kept.)"""
+        if add_noise:
+            if mu is None or sigma is None:
+                raise ValueError('Arguments "mu" and "sigma" are required '
+                                 'when argument "add_noise" is set to True.')
+            array = np.random.normal(mu, sigma, cls.TILE_SIZE ** 2).astype(np.uint8)
+        else:
+            array = np.zeros((cls.TILE_SIZE,) * 2, dtype=np.uint8)
+        return cls(array, metadata)
 
 
 class IllumstatsImage(Image):

@@ -89,6 +89,21 @@ class ChannelImageMetadata(SiteImageMetadata):
             self.__class__.__name__, self.channel_id, self.site_id, self.cycle_id, self.tpoint)
 
 
+class PyramidTileMetadata(object):
+    """Metadata of a ``PyramidTile`` (tmlib/metadata.py:447-474): plain
+    attributes, no type checks, and not an ``ImageMetadata``."""
+
+    def __init__(self, z, y, x, channel_layer_id):
+        self.z = z
+        self.y = y
+        self.x = x
+        self.channel_layer_id = channel_layer_id
+
+    def __repr__(self):
+        return "%s(z=%r, y=%r, x=%r, channel_layer_id=%r)" % (
+            self.__class__.__name__, self.z, self.y, self.x, self.channel_layer_id)
+
+
 class IllumstatsImageMetadata(ImageMetadata):
     """Metadata of an ``IllumstatsImage`` (tmlib/metadata.py:477-522)."""
 
