@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TMH_ABI_VERSION 5
+#define TMH_ABI_VERSION 6
 
 #define TMH_OK 0
 #define TMH_EINVAL (-22)  /* bad argument: maps to ValueError / TypeError */
@@ -475,6 +475,39 @@ int tmh_pyramid_shrink2_device(const uint8_t* dev_src, int src_rows, int src_col
                                void* stream);
 int tmh_pyramid_shrink2(const uint8_t* host_src, int src_rows, int src_cols, int src_last_h,
                         int src_last_w, uint8_t* host_dst, int* dst_last_h, int* dst_last_w);
+/* JPEG-code every tile of one tile-major level: what PyramidTile.jpeg_encode
+ * (image.py:1073-1094, cv2.imencode('.jpeg', array, [IMWRITE_JPEG_QUALITY,
+ * quality])) returns for each tile and ChannelLayerTile.pixels stores
+ * (models/tile.py:107-122), for all rows x cols tiles in one call.  The first
+ * five arguments are a level as the calls above leave it: tile (y, x) is
+ * last_h high in the last row, last_w wide in the last column (1..256), 256
+ * otherwise, and only that extent is the image -- the bytes around a ragged
+ * tile are not read as samples.  Every file is the baseline JPEG libjpeg
+ * writes for one 8-bit grayscale component, byte for byte: SOI, APP0 JFIF
+ * 1.01 (no units, density 1 x 1), DQT (table 0 of jpeg_set_quality(quality,
+ * force_baseline), quality clamped to 1..100), SOF0 with the tile's height
+ * and width, the Annex K.3 / K.5 luminance Huffman tables, SOS, the
+ * entropy-coded segment and EOI -- a 328-byte header; blocks padded by
+ * replicating the last column, then the last row; jfdctint.c's slow-integer
+ * DCT; one DC predictor per tile, no restart markers; 0xFF bytes stuffed, the
+ * last byte filled with 1 bits.
+ * dev_offsets[rows * cols + 1] is always filled: offsets[0] = 0, then the
+ * exclusive scan of the exact file sizes in row-major tile order; *total
+ * (host) = offsets[rows * cols].  dev_out NULL: the call only measures.
+ * Otherwise tile t's file is written at dev_out + offsets[t] (one compact
+ * blob; no byte past *total is touched); out_capacity < *total: TMH_EINVAL
+ * with *total set and nothing written to dev_out.  A NULL level, offsets or
+ * total, rows or cols < 1, last_h or last_w outside 1..256: TMH_EINVAL,
+ * nothing launched.  dev_level 16-byte, dev_offsets 8-byte aligned.  A level
+ * is coded once to measure and, when writing, once more at the offsets; work
+ * is queued on `stream` (NULL: the default stream) and the call returns when
+ * the result is complete. */
+int tmh_jpeg_encode_level_device(const uint8_t* dev_level, int rows, int cols, int last_h,
+                                 int last_w, int quality, uint8_t* dev_out, int64_t out_capacity,
+                                 int64_t* dev_offsets, int64_t* total, void* stream);
+int tmh_jpeg_encode_level(const uint8_t* host_level, int rows, int cols, int last_h, int last_w,
+                          int quality, uint8_t* host_out, int64_t out_capacity,
+                          int64_t* host_offsets, int64_t* total);
 
 /* ChannelImage.clip alone (image.py:589), u16. */
 int tmh_clip_u16(const uint16_t* host_in, uint16_t* host_out, int64_t n, int lo, int hi);

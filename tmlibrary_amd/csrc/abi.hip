@@ -2236,6 +2236,73 @@ int tmh_pyramid_shrink2(const uint8_t* host_src, int src_rows, int src_cols, int
   });
 }
 
+static void check_jpeg_args(const void* level, int rows, int cols, int last_h, int last_w,
+                            const void* out, int64_t out_capacity, const void* offsets,
+                            const void* total) {
+  TMH_CHECK(level && offsets && total, TMH_EINVAL, "level, offsets or total pointer is NULL");
+  TMH_CHECK(rows >= 1 && cols >= 1, TMH_EINVAL, "sizes must be positive");
+  TMH_CHECK((int64_t)rows * cols < (int64_t(1) << 31) - 1, TMH_EINVAL, "more than 2^31 tiles");
+  TMH_CHECK(last_h >= 1 && last_h <= kPyrTile && last_w >= 1 && last_w <= kPyrTile, TMH_EINVAL,
+            "last tile row height / column width must be in 1..256");
+  TMH_CHECK(!out || out_capacity >= 0, TMH_EINVAL, "negative output capacity");
+}
+
+int tmh_jpeg_encode_level_device(const uint8_t* dev_level, int rows, int cols, int last_h,
+                                 int last_w, int quality, uint8_t* dev_out, int64_t out_capacity,
+                                 int64_t* dev_offsets, int64_t* total, void* stream) {
+  return guard([&] {
+    check_jpeg_args(dev_level, rows, cols, last_h, last_w, dev_out, out_capacity, dev_offsets,
+                    total);
+    TMH_CHECK((reinterpret_cast<uintptr_t>(dev_level) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(dev_offsets) & 7) == 0,
+              TMH_EINVAL, "the level must be 16-byte and the offsets 8-byte aligned");
+    const hipStream_t s = (hipStream_t)stream;
+    const int64_t n = (int64_t)rows * cols;
+    std::vector<uint8_t> tab(jpeg_tables_bytes());
+    jpeg_tables_host(quality, tab.data());
+    DBuf<uint8_t> d_tab;
+    d_tab.alloc(tab.size());
+    TMH_HIP(hipMemcpyAsync(d_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, s));
+    launch_jpeg_measure(dev_level, rows, cols, last_h, last_w, d_tab.p, dev_offsets, s);
+    TMH_HIP(hipMemcpyAsync(total, dev_offsets + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    TMH_HIP(hipStreamSynchronize(s));
+    if (!dev_out) return;
+    TMH_CHECK(out_capacity >= *total, TMH_EINVAL,
+              "the output holds " + std::to_string(out_capacity) + " bytes, the level's files " +
+                  std::to_string(*total));
+    launch_jpeg_write(dev_level, rows, cols, last_h, last_w, d_tab.p, dev_offsets, dev_out, s);
+    TMH_HIP(hipStreamSynchronize(s));  // complete on return; the tables are freed
+  });
+}
+
+int tmh_jpeg_encode_level(const uint8_t* host_level, int rows, int cols, int last_h, int last_w,
+                          int quality, uint8_t* host_out, int64_t out_capacity,
+                          int64_t* host_offsets, int64_t* total) {
+  return guard([&] {
+    check_jpeg_args(host_level, rows, cols, last_h, last_w, host_out, out_capacity, host_offsets,
+                    total);
+    const size_t n = (size_t)rows * cols, in_b = n * kPyrTile * kPyrTile;
+    DBuf<uint8_t> a, b;
+    DBuf<int64_t> off;
+    a.alloc(in_b);
+    off.alloc(n + 1);
+    TMH_HIP(hipMemcpy(a.p, host_level, in_b, hipMemcpyHostToDevice));
+    int rc = tmh_jpeg_encode_level_device(a.p, rows, cols, last_h, last_w, quality, nullptr, 0,
+                                          off.p, total, nullptr);
+    if (rc) throw Error{rc, g_last_error};
+    TMH_HIP(hipMemcpy(host_offsets, off.p, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (!host_out) return;
+    TMH_CHECK(out_capacity >= *total, TMH_EINVAL,
+              "the output holds " + std::to_string(out_capacity) + " bytes, the level's files " +
+                  std::to_string(*total));
+    b.alloc((size_t)*total);
+    rc = tmh_jpeg_encode_level_device(a.p, rows, cols, last_h, last_w, quality, b.p, *total, off.p,
+                                      total, nullptr);
+    if (rc) throw Error{rc, g_last_error};
+    TMH_HIP(hipMemcpy(host_out, b.p, (size_t)*total, hipMemcpyDeviceToHost));
+  });
+}
+
 int tmh_clip_u16(const uint16_t* host_in, uint16_t* host_out, int64_t n, int lo, int hi) {
   return guard([&] {
     TMH_CHECK((host_in && host_out) || n == 0, TMH_EINVAL, "bad arguments");

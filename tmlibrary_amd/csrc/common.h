@@ -448,6 +448,16 @@ void launch_tiles_base(const uint8_t* sites, int64_t n_sites, int H, int W,
                        int64_t n_tiles, hipStream_t s);
 void launch_pyramid_shrink2(const uint8_t* src, int R, int C, int last_h, int last_w, uint8_t* dst,
                             hipStream_t s);
+// JPEG coding of a tile-major level (jpeg_kernels.hip).  tables: the call's
+// JpegTables (jpeg_core.h), jpeg_tables_bytes() bytes, built by
+// jpeg_tables_host and uploaded by the caller.  measure: offsets[n + 1] = the
+// exclusive scan of the files' sizes; write: every file at out + offsets[t].
+size_t jpeg_tables_bytes();
+void jpeg_tables_host(int quality, void* tables);
+void launch_jpeg_measure(const uint8_t* level, int rows, int cols, int last_h, int last_w,
+                         const void* d_tables, int64_t* offsets, hipStream_t s);
+void launch_jpeg_write(const uint8_t* level, int rows, int cols, int last_h, int last_w,
+                       const void* d_tables, const int64_t* offsets, uint8_t* out, hipStream_t s);
 void launch_clip_u16(const uint16_t* in, uint16_t* out, int64_t n, int lo, int hi, hipStream_t s);
 void launch_synth(uint16_t* out, int64_t n_sites, int H, int W, uint64_t seed, int channel,
                   int64_t first_site, int dist, hipStream_t s);

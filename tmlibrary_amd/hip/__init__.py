@@ -33,7 +33,7 @@ TMH_FUSED_NO_HIST = 100
 TMH_SYNTH_STANDARD = 0
 TMH_SYNTH_BRIGHT = 1
 TMH_SYNTH_UNIFORM = 2
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _P = C.c_void_p
 _I64 = C.c_int64
@@ -104,6 +104,8 @@ SIGNATURES = {
     "tmh_tiles_base": (_I, [_P, _I64, _I, _I, _P, _I64, _P, _I, _I]),
     "tmh_pyramid_shrink2_device": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(_I), C.POINTER(_I), _P]),
     "tmh_pyramid_shrink2": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(_I), C.POINTER(_I)]),
+    "tmh_jpeg_encode_level_device": (_I, [_P, _I, _I, _I, _I, _I, _P, _I64, _P, C.POINTER(_I64), _P]),
+    "tmh_jpeg_encode_level": (_I, [_P, _I, _I, _I, _I, _I, _P, _I64, _P, C.POINTER(_I64)]),
     "tmh_synth_sites_device": (_I, [_P, _I64, _I, _I, C.c_uint64, _I, _I64, _I, _P]),
     "tmh_synth_tables": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "tmh_box_probe_device": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I, _P, C.POINTER(_D),

@@ -514,8 +514,9 @@ class Corrector(object):
 
 
 class PyramidTile(Image):
-    """A pyramid tile: uint8, at most 256 x 256 pixels (tmlib/image.py:927-1071;
-    the JPEG codec methods are not mirrored)."""
+    """A pyramid tile: uint8, at most 256 x 256 pixels (tmlib/image.py:927-1094).
+    ``jpeg_encode`` runs on the device; the JPEG decoders ``create_from_binary``
+    and ``create_from_buffer`` (image.py:967-1037) are not mirrored."""
 
     TILE_SIZE = 256
 
@@ -569,6 +570,25 @@ class PyramidTile(Image):
         else:
             array = np.zeros((cls.TILE_SIZE,) * 2, dtype=np.uint8)
         return cls(array, metadata)
+
+    def jpeg_encode(self, quality=95):
+        """image.py:1073-1094: the tile's JPEG file as a 1-D uint8 array --
+        the bytes ``cv2.imencode('.jpeg', array, [cv2.IMWRITE_JPEG_QUALITY,
+        quality])`` produces through libjpeg, coded on the device
+        (``tmh_jpeg_encode_level`` over a level of this one tile;
+        ``Pyramid.encode_level`` codes a whole level in one call)."""
+        h, w = self.array.shape
+        full = np.zeros((self.TILE_SIZE,) * 2, dtype=np.uint8)
+        full[:h, :w] = self.array
+        L = hip.lib()
+        offsets = np.zeros(2, dtype=np.int64)
+        total = C.c_int64(0)
+        hip.check(L.tmh_jpeg_encode_level(hip.ptr(full), 1, 1, h, w, int(quality), None, 0,
+                                          hip.ptr(offsets), C.byref(total)))
+        out = np.empty(total.value, dtype=np.uint8)
+        hip.check(L.tmh_jpeg_encode_level(hip.ptr(full), 1, 1, h, w, int(quality), hip.ptr(out),
+                                          out.nbytes, hip.ptr(offsets), C.byref(total)))
+        return out
 
 
 class IllumstatsImage(Image):

@@ -14,6 +14,10 @@ over plain data (no ORM rows), ``plan_base_tiles`` turns the reference's
 per-site loop into one flat table of rectangles, and ``build_pyramid`` runs
 the two device passes (``tmh_tiles_base_device``,
 ``tmh_pyramid_shrink2_device``) over sites that are already resident.
+``Pyramid.encode_level`` / ``Pyramid.iter_jpeg_tiles`` then code the tiles as
+the JPEG files the reference stores in ``ChannelLayerTile.pixels``
+(tmlib/models/tile.py:107-122), a level per call
+(``tmh_jpeg_encode_level_device``).
 
 Everything in this module except ``build_pyramid`` / ``Pyramid`` is host-only
 numpy and needs no device.
@@ -442,6 +446,29 @@ def _device_pointer(x):
     raise TypeError("sites_u8 must be a uint8 numpy array or a device pointer")
 
 
+class EncodedLevel(object):
+    """The JPEG files of one level: ``blob`` (1-D uint8, host) holds them back
+    to back in row-major tile order, tile (y, x)'s at ``offsets[y * cols + x]
+    : offsets[y * cols + x + 1]`` (int64, tiles + 1 entries); ``dimensions``:
+    the level's (tile rows, tile columns)."""
+
+    def __init__(self, blob, offsets, dimensions):
+        self.blob = blob
+        self.offsets = offsets
+        self.dimensions = (int(dimensions[0]), int(dimensions[1]))
+
+    def tile(self, y, x):
+        """The file of tile (y, x) as ``bytes``."""
+        rows, cols = self.dimensions
+        if not (0 <= y < rows and 0 <= x < cols):
+            raise IndexError("tile (%d, %d) outside the level's %d x %d tiles" % (y, x, rows, cols))
+        t = y * cols + x
+        return self.blob[self.offsets[t]:self.offsets[t + 1]].tobytes()
+
+    def __len__(self):
+        return self.dimensions[0] * self.dimensions[1]
+
+
 class Pyramid(object):
     """All levels of a layer's pyramid, resident on the device until
     ``close()`` (about 4/3 x 64 KB per base tile).  Level ``z`` is
@@ -505,6 +532,45 @@ class Pyramid(object):
         column's width) of level z's tile-major storage."""
         self._check(z)
         return (self._levels[z],) + tuple(self.dimensions[z]) + tuple(self._last[z])
+
+    def encode_level(self, z, quality=95, stream=None):
+        """Every tile of level z as the JPEG file ``PyramidTile.jpeg_encode``
+        (tmlib/image.py:1073-1094) returns for it: an ``EncodedLevel``.  One
+        measuring call, one allocation of the exact size, one writing call and
+        one device-to-host copy of the blob."""
+        self._check(z)
+        L = hip.lib()
+        level = self.device_level(z)
+        n = level[1] * level[2]
+        d_off, d_out = C.c_void_p(), C.c_void_p()
+        total = C.c_int64(0)
+        try:
+            hip.check(L.tmh_malloc_device(C.byref(d_off), (n + 1) * 8))
+            hip.check(L.tmh_jpeg_encode_level_device(*level, int(quality), None, 0, d_off,
+                                                     C.byref(total), stream))
+            hip.check(L.tmh_malloc_device(C.byref(d_out), total.value))
+            hip.check(L.tmh_jpeg_encode_level_device(*level, int(quality), d_out, total.value,
+                                                     d_off, C.byref(total), stream))
+            blob = np.empty(total.value, dtype=np.uint8)
+            offsets = np.empty(n + 1, dtype=np.int64)
+            hip.check(L.tmh_memcpy(hip.ptr(blob), d_out, blob.nbytes, 1, stream))
+            hip.check(L.tmh_memcpy(hip.ptr(offsets), d_off, offsets.nbytes, 1, stream))
+        finally:
+            for p in (d_off, d_out):
+                if p.value:
+                    L.tmh_free_device(p)
+        return EncodedLevel(blob, offsets, self.dimensions[z])
+
+    def iter_jpeg_tiles(self, quality=95):
+        """``(z, y, x, bytes)`` of every tile of every level -- the rows of
+        the reference's ``channel_layer_tiles`` table without the layer id --
+        the base level first, then upward; row-major within a level.  One
+        level is coded at a time, so the host holds one level's blob."""
+        for z in range(self.depth - 1, -1, -1):
+            enc = self.encode_level(z, quality)
+            rows, cols = enc.dimensions
+            for y, x in itertools.product(range(rows), range(cols)):
+                yield z, y, x, enc.tile(y, x)
 
     def close(self):
         self._closed = True
