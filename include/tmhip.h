@@ -508,6 +508,64 @@ int tmh_jpeg_encode_level_device(const uint8_t* dev_level, int rows, int cols, i
 int tmh_jpeg_encode_level(const uint8_t* host_level, int rows, int cols, int last_h, int last_w,
                           int quality, uint8_t* host_out, int64_t out_capacity,
                           int64_t* host_offsets, int64_t* total);
+/* Every tile of a level as libjpeg decodes it from the file
+ * tmh_jpeg_encode_level writes for it at `quality`: what the getter
+ * ChannelLayerTile.pixels (models/tile.py:97-105, PyramidTile.create_from_binary,
+ * cv2.imdecode) hands to _create_lower_zoom_level_tiles (illuminati/api.py:
+ * 503-573) when it reads the level above.  No file is made: Huffman coding is
+ * lossless, so per 8 x 8 block (padded by replicating the last column, then the
+ * last row) it is the encoder's forward DCT and quantiser, then coefficient x
+ * the file's 8-bit quantiser, jidctint.c's slow-integer inverse DCT
+ * (jpeg_idct_islow: columns first with DESCALE by 11, then rows with DESCALE by
+ * 18) and the range limit clamp(v + 128, 0, 255), cropped to the tile's
+ * extent.  The first five arguments are a level as for the encoder; dev_out
+ * has the same layout and every byte of it is written once: the decoded
+ * samples inside a tile's extent, 0 around a ragged tile.  A NULL pointer, rows
+ * or cols < 1, last_h or last_w outside 1..256, dev_out == dev_level (the
+ * levels must not overlap): TMH_EINVAL, nothing launched.  Both 16-byte
+ * aligned.  Asynchronous on `stream` (NULL: the default stream); the host form
+ * is synchronous. */
+int tmh_jpeg_roundtrip_level_device(const uint8_t* dev_level, int rows, int cols, int last_h,
+                                    int last_w, int quality, uint8_t* dev_out, void* stream);
+int tmh_jpeg_roundtrip_level(const uint8_t* host_level, int rows, int cols, int last_h, int last_w,
+                             int quality, uint8_t* host_out);
+/* Decode n stored tile files (PyramidTile.create_from_binary, image.py:993-1037)
+ * in one call.  File t is dev_blob[offsets[t] .. offsets[t + 1]) (offsets: n + 1
+ * entries, not decreasing; an EncodedLevel's blob and offsets fit as they are).
+ * Tile t is written to dev_tiles + t * 65536 in the level storage's form: the
+ * picture at a 256-byte pitch in the corner, 0 around it; dims[2 t], dims[2 t
+ * + 1] = its height and width; status[t] = 0.  A file that is not decoded
+ * leaves a tile of zeros, dims (0, 0) and status 1 (well formed but not
+ * supported) or 2 (corrupt); the call still returns TMH_OK.
+ * Decoded: every file libjpeg writes for one 8-bit grayscale component with
+ * default settings at any quality -- SOI; APPn, COM and unknown segments
+ * passed over; DQT 8-bit, table 0, values 1..255 (other table ids ignored);
+ * SOF0 with precision 8, one component sampled 1 x 1 using table 0, height and
+ * width in 1..256; DHT class 0 and 1, id 0, equal to Annex K.3 / K.5, one or
+ * several tables to a segment; DRI with interval 0; SOS with Ss 0, Se 63, Ah
+ * = Al = 0; one DC predictor, 0xFF 0x00 unstuffed; EOI directly after the last
+ * block's padded byte (bytes after EOI are ignored).  The pixels are
+ * libjpeg's: tmh_jpeg_roundtrip_level's arithmetic.
+ * Status 1: SOF1, SOF2 and above, DNL or arithmetic conditioning; precision
+ * other than 8; more than one component; other sampling or table selectors;
+ * a side of 0 or above 256; a 16-bit or missing table 0 DQT; missing or
+ * non-Annex-K Huffman tables; a non-zero restart interval; a scan that is not
+ * 0..63 / 0.  Status 2: no SOI; a header or segment that does not fit the file
+ * or is malformed; a zero quantiser; the coded data ending (or a marker
+ * standing) before the last block is complete; a bit pattern that is no code;
+ * a run past coefficient 63; a DC category above 11, an AC size above 10 or a
+ * DC value outside -2048..2047; anything but EOI after the last block.
+ * For any bytes no read leaves a file's range and no write its tile's 64 KB.
+ * n < 0, a NULL pointer (n > 0; offsets always) or, in the host form,
+ * decreasing or negative offsets: TMH_EINVAL, nothing launched.  n = 0 does
+ * nothing.  dev_tiles 16-byte, dev_offsets 8-byte, dims and status 4-byte
+ * aligned.  Queued on `stream` (NULL: the default stream); the call returns
+ * when the result is complete. */
+int tmh_jpeg_decode_tiles_device(const uint8_t* dev_blob, const int64_t* dev_offsets, int64_t n,
+                                 uint8_t* dev_tiles, int32_t* dev_dims, int32_t* dev_status,
+                                 void* stream);
+int tmh_jpeg_decode_tiles(const uint8_t* host_blob, const int64_t* host_offsets, int64_t n,
+                          uint8_t* host_tiles, int32_t* host_dims, int32_t* host_status);
 
 /* ChannelImage.clip alone (image.py:589), u16. */
 int tmh_clip_u16(const uint16_t* host_in, uint16_t* host_out, int64_t n, int lo, int hi);

@@ -2303,6 +2303,99 @@ int tmh_jpeg_encode_level(const uint8_t* host_level, int rows, int cols, int las
   });
 }
 
+static void check_roundtrip_args(const void* level, int rows, int cols, int last_h, int last_w,
+                                 const void* out) {
+  TMH_CHECK(level && out, TMH_EINVAL, "level or output pointer is NULL");
+  TMH_CHECK(rows >= 1 && cols >= 1, TMH_EINVAL, "sizes must be positive");
+  TMH_CHECK((int64_t)rows * cols < (int64_t(1) << 31) - 1, TMH_EINVAL, "more than 2^31 tiles");
+  TMH_CHECK(last_h >= 1 && last_h <= kPyrTile && last_w >= 1 && last_w <= kPyrTile, TMH_EINVAL,
+            "last tile row height / column width must be in 1..256");
+  TMH_CHECK(level != out, TMH_EINVAL, "level and output must be distinct");
+}
+
+int tmh_jpeg_roundtrip_level_device(const uint8_t* dev_level, int rows, int cols, int last_h,
+                                    int last_w, int quality, uint8_t* dev_out, void* stream) {
+  return guard([&] {
+    check_roundtrip_args(dev_level, rows, cols, last_h, last_w, dev_out);
+    TMH_CHECK(((reinterpret_cast<uintptr_t>(dev_level) | reinterpret_cast<uintptr_t>(dev_out)) & 15) == 0,
+              TMH_EINVAL, "levels must be 16-byte aligned");
+    launch_jpeg_roundtrip(dev_level, rows, cols, last_h, last_w, quality, dev_out,
+                          (hipStream_t)stream);
+  });
+}
+
+int tmh_jpeg_roundtrip_level(const uint8_t* host_level, int rows, int cols, int last_h, int last_w,
+                             int quality, uint8_t* host_out) {
+  return guard([&] {
+    check_roundtrip_args(host_level, rows, cols, last_h, last_w, host_out);
+    const size_t bytes = (size_t)rows * cols * kPyrTile * kPyrTile;
+    DBuf<uint8_t> a, b;
+    a.alloc(bytes);
+    b.alloc(bytes);
+    TMH_HIP(hipMemcpy(a.p, host_level, bytes, hipMemcpyHostToDevice));
+    int rc = tmh_jpeg_roundtrip_level_device(a.p, rows, cols, last_h, last_w, quality, b.p, nullptr);
+    if (rc) throw Error{rc, g_last_error};
+    TMH_HIP(hipStreamSynchronize(nullptr));
+    TMH_HIP(hipMemcpy(host_out, b.p, bytes, hipMemcpyDeviceToHost));
+  });
+}
+
+static void check_decode_args(const void* blob, const void* offsets, int64_t n, const void* tiles,
+                              const void* dims, const void* status) {
+  TMH_CHECK(n >= 0 && n < (int64_t(1) << 31) - 1, TMH_EINVAL, "file count must be in 0..2^31-2");
+  TMH_CHECK(offsets, TMH_EINVAL, "offsets pointer is NULL");
+  TMH_CHECK(n == 0 || (blob && tiles && dims && status), TMH_EINVAL,
+            "blob, tiles, dims or status pointer is NULL");
+}
+
+int tmh_jpeg_decode_tiles_device(const uint8_t* dev_blob, const int64_t* dev_offsets, int64_t n,
+                                 uint8_t* dev_tiles, int32_t* dev_dims, int32_t* dev_status,
+                                 void* stream) {
+  return guard([&] {
+    check_decode_args(dev_blob, dev_offsets, n, dev_tiles, dev_dims, dev_status);
+    TMH_CHECK((reinterpret_cast<uintptr_t>(dev_tiles) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(dev_offsets) & 7) == 0 &&
+                  ((reinterpret_cast<uintptr_t>(dev_dims) | reinterpret_cast<uintptr_t>(dev_status)) & 3) == 0,
+              TMH_EINVAL, "tiles must be 16-byte, offsets 8-byte, dims and status 4-byte aligned");
+    if (n == 0) return;
+    const hipStream_t s = (hipStream_t)stream;
+    std::vector<uint8_t> tab(jpeg_decode_tables_bytes());
+    jpeg_decode_tables_host(tab.data());
+    DBuf<uint8_t> d_tab;
+    d_tab.alloc(tab.size());
+    TMH_HIP(hipMemcpyAsync(d_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, s));
+    launch_jpeg_decode_tiles(dev_blob, dev_offsets, n, d_tab.p, dev_tiles, dev_dims, dev_status, s);
+    TMH_HIP(hipStreamSynchronize(s));  // complete on return; the tables are freed
+  });
+}
+
+int tmh_jpeg_decode_tiles(const uint8_t* host_blob, const int64_t* host_offsets, int64_t n,
+                          uint8_t* host_tiles, int32_t* host_dims, int32_t* host_status) {
+  return guard([&] {
+    check_decode_args(host_blob, host_offsets, n, host_tiles, host_dims, host_status);
+    if (n == 0) return;
+    TMH_CHECK(host_offsets[0] >= 0, TMH_EINVAL, "offsets must not be negative");
+    for (int64_t i = 0; i < n; ++i)
+      TMH_CHECK(host_offsets[i + 1] >= host_offsets[i], TMH_EINVAL, "offsets must not decrease");
+    const size_t blob_b = (size_t)host_offsets[n], tiles_b = (size_t)n * kPyrTile * kPyrTile;
+    DBuf<uint8_t> blob, tiles;
+    DBuf<int64_t> off;
+    DBuf<int32_t> dims, status;
+    blob.alloc(blob_b ? blob_b : 1);
+    tiles.alloc(tiles_b);
+    off.alloc((size_t)n + 1);
+    dims.alloc(2 * (size_t)n);
+    status.alloc((size_t)n);
+    TMH_HIP(hipMemcpy(blob.p, host_blob, blob_b, hipMemcpyHostToDevice));
+    TMH_HIP(hipMemcpy(off.p, host_offsets, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    int rc = tmh_jpeg_decode_tiles_device(blob.p, off.p, n, tiles.p, dims.p, status.p, nullptr);
+    if (rc) throw Error{rc, g_last_error};
+    TMH_HIP(hipMemcpy(host_tiles, tiles.p, tiles_b, hipMemcpyDeviceToHost));
+    TMH_HIP(hipMemcpy(host_dims, dims.p, 2 * (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    TMH_HIP(hipMemcpy(host_status, status.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  });
+}
+
 int tmh_clip_u16(const uint16_t* host_in, uint16_t* host_out, int64_t n, int lo, int hi) {
   return guard([&] {
     TMH_CHECK((host_in && host_out) || n == 0, TMH_EINVAL, "bad arguments");

@@ -458,6 +458,18 @@ void launch_jpeg_measure(const uint8_t* level, int rows, int cols, int last_h, i
                          const void* d_tables, int64_t* offsets, hipStream_t s);
 void launch_jpeg_write(const uint8_t* level, int rows, int cols, int last_h, int last_w,
                        const void* d_tables, const int64_t* offsets, uint8_t* out, hipStream_t s);
+// JPEG decoding (jpeg_decode_kernels.hip).  roundtrip: every tile of a level as
+// libjpeg decodes it from the file launch_jpeg_write writes for it at `quality`
+// (out: the same layout, distinct from level).  decode_tiles: n files at
+// blob + offsets[t] into tile storage, dims[n][2] and status[n]; d_tables:
+// jpeg_decode_tables_bytes() bytes built by jpeg_decode_tables_host.
+void launch_jpeg_roundtrip(const uint8_t* level, int rows, int cols, int last_h, int last_w,
+                           int quality, uint8_t* out, hipStream_t s);
+size_t jpeg_decode_tables_bytes();
+void jpeg_decode_tables_host(void* tables);
+void launch_jpeg_decode_tiles(const uint8_t* blob, const int64_t* offsets, int64_t n,
+                              const void* d_tables, uint8_t* tiles, int32_t* dims,
+                              int32_t* status, hipStream_t s);
 void launch_clip_u16(const uint16_t* in, uint16_t* out, int64_t n, int lo, int hi, hipStream_t s);
 void launch_synth(uint16_t* out, int64_t n_sites, int H, int W, uint64_t seed, int channel,
                   int64_t first_site, int dist, hipStream_t s);

@@ -106,6 +106,10 @@ SIGNATURES = {
     "tmh_pyramid_shrink2": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(_I), C.POINTER(_I)]),
     "tmh_jpeg_encode_level_device": (_I, [_P, _I, _I, _I, _I, _I, _P, _I64, _P, C.POINTER(_I64), _P]),
     "tmh_jpeg_encode_level": (_I, [_P, _I, _I, _I, _I, _I, _P, _I64, _P, C.POINTER(_I64)]),
+    "tmh_jpeg_roundtrip_level_device": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "tmh_jpeg_roundtrip_level": (_I, [_P, _I, _I, _I, _I, _I, _P]),
+    "tmh_jpeg_decode_tiles_device": (_I, [_P, _P, _I64, _P, _P, _P, _P]),
+    "tmh_jpeg_decode_tiles": (_I, [_P, _P, _I64, _P, _P, _P]),
     "tmh_synth_sites_device": (_I, [_P, _I64, _I, _I, C.c_uint64, _I, _I64, _I, _P]),
     "tmh_synth_tables": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "tmh_box_probe_device": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I, _P, C.POINTER(_D),

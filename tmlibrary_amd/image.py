@@ -286,6 +286,27 @@ def tiles_to_array(tiles: np.ndarray, last_h: int, last_w: int) -> np.ndarray:
     return np.ascontiguousarray(full[:(rows - 1) * _TILE + last_h, :(cols - 1) * _TILE + last_w])
 
 
+#: status of a file given to the JPEG decoder (tmh_jpeg_decode_tiles)
+JPEG_STATUS = {0: "ok", 1: "unsupported", 2: "corrupt"}
+
+
+def decode_jpeg_blob(blob: np.ndarray, offsets: np.ndarray):
+    """JPEG files ``blob[offsets[t]:offsets[t + 1]]`` decoded on the device
+    (``tmh_jpeg_decode_tiles``): ``(tiles [n][256][256] uint8 with each
+    picture in its corner, dims [n][2] int32, status [n] int32)``."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = len(offsets) - 1
+    if n < 0 or (n and offsets[-1] > blob.size):
+        raise ValueError("offsets do not fit the blob")
+    tiles = np.empty((n, _TILE, _TILE), dtype=np.uint8)
+    dims = np.empty((n, 2), dtype=np.int32)
+    status = np.empty(n, dtype=np.int32)
+    hip.check(hip.lib().tmh_jpeg_decode_tiles(hip.ptr(blob), hip.ptr(offsets), n, hip.ptr(tiles),
+                                              hip.ptr(dims), hip.ptr(status)))
+    return tiles, dims, status
+
+
 def shrink2_array(array: np.ndarray) -> np.ndarray:
     """A uint8 array with even sides halved on the device (tmh_pyramid_shrink2)."""
     a = np.ascontiguousarray(array)
@@ -515,8 +536,8 @@ class Corrector(object):
 
 class PyramidTile(Image):
     """A pyramid tile: uint8, at most 256 x 256 pixels (tmlib/image.py:927-1094).
-    ``jpeg_encode`` runs on the device; the JPEG decoders ``create_from_binary``
-    and ``create_from_buffer`` (image.py:967-1037) are not mirrored."""
+    ``jpeg_encode`` and the JPEG decoders ``create_from_binary`` /
+    ``create_from_buffer`` (image.py:993-1037) run on the device."""
 
     TILE_SIZE = 256
 
@@ -570,6 +591,25 @@ class PyramidTile(Image):
         else:
             array = np.zeros((cls.TILE_SIZE,) * 2, dtype=np.uint8)
         return cls(array, metadata)
+
+    @classmethod
+    def create_from_binary(cls, string, metadata=None):
+        """image.py:993-1014: the tile of a JPEG file given as a binary string
+        -- the pixels ``cv2.imdecode`` returns through libjpeg, decoded on the
+        device (``tmh_jpeg_decode_tiles`` over this one file;
+        ``workflow.pyramid.decode_jpeg_tiles`` decodes many in one call).  A
+        file the decoder does not take raises ``ValueError``."""
+        return cls.create_from_buffer(string, metadata)
+
+    @classmethod
+    def create_from_buffer(cls, buf, metadata=None):
+        """image.py:1016-1037: as ``create_from_binary``, from a buffer object."""
+        data = np.frombuffer(buf, np.uint8)
+        tiles, dims, status = decode_jpeg_blob(data, np.array([0, data.size], dtype=np.int64))
+        if status[0]:
+            raise ValueError("not a JPEG file this decoder takes: %s"
+                             % JPEG_STATUS.get(int(status[0]), status[0]))
+        return cls(np.ascontiguousarray(tiles[0, :dims[0, 0], :dims[0, 1]]), metadata)
 
     def jpeg_encode(self, quality=95):
         """image.py:1073-1094: the tile's JPEG file as a 1-D uint8 array --

@@ -17,7 +17,12 @@ the two device passes (``tmh_tiles_base_device``,
 ``Pyramid.encode_level`` / ``Pyramid.iter_jpeg_tiles`` then code the tiles as
 the JPEG files the reference stores in ``ChannelLayerTile.pixels``
 (tmlib/models/tile.py:107-122), a level per call
-(``tmh_jpeg_encode_level_device``).
+(``tmh_jpeg_encode_level_device``).  With ``jpeg_quality`` the pyramid is the one
+the reference stores: it reads each level back through the JPEG decoder
+(``ChannelLayerTile.pixels``, tmlib/models/tile.py:97-105) before halving it,
+so every level below the base is built from the JPEG round trip of the level
+above (``tmh_jpeg_roundtrip_level_device``).  ``decode_jpeg_tiles`` /
+``EncodedLevel.decode`` read stored files back (``tmh_jpeg_decode_tiles``).
 
 Everything in this module except ``build_pyramid`` / ``Pyramid`` is host-only
 numpy and needs no device.
@@ -31,7 +36,7 @@ import itertools
 import numpy as np
 
 from .. import hip
-from ..image import PyramidTile, tiles_to_array
+from ..image import JPEG_STATUS, PyramidTile, decode_jpeg_blob, tiles_to_array
 from ..metadata import PyramidTileMetadata
 
 TILE_SIZE = 256
@@ -468,15 +473,59 @@ class EncodedLevel(object):
     def __len__(self):
         return self.dimensions[0] * self.dimensions[1]
 
+    def decode(self):
+        """The level decoded from its files, stitched into one array as
+        ``Pyramid.level`` returns it (on a stored pyramid:
+        ``Pyramid.decoded_level``).  Raises ``ValueError`` for a file the
+        decoder does not take, or sizes that are no level's."""
+        rows, cols = self.dimensions
+        tiles, dims, status = decode_jpeg_blob(self.blob, self.offsets)
+        _raise_for_status(status)
+        dims = dims.reshape(rows, cols, 2)
+        last_h, last_w = int(dims[-1, -1, 0]), int(dims[-1, -1, 1])
+        want_h = np.where(np.arange(rows) == rows - 1, last_h, TILE_SIZE)[:, None]
+        want_w = np.where(np.arange(cols) == cols - 1, last_w, TILE_SIZE)[None, :]
+        if np.any(dims[..., 0] != want_h) or np.any(dims[..., 1] != want_w):
+            raise ValueError("the files' sizes are not those of one level")
+        return tiles_to_array(tiles.reshape(rows, cols, TILE_SIZE, TILE_SIZE), last_h, last_w)
+
+
+def _raise_for_status(status):
+    bad = np.flatnonzero(status)
+    if len(bad):
+        raise ValueError("JPEG file %d is %s (status %d)"
+                         % (bad[0], JPEG_STATUS.get(int(status[bad[0]]), "not decoded"),
+                            status[bad[0]]))
+
+
+def decode_jpeg_tiles(files):
+    """The pictures of JPEG files (``bytes`` or uint8 arrays, as
+    ``EncodedLevel.tile`` / ``iter_jpeg_tiles`` / ``PyramidTile.jpeg_encode``
+    give them), decoded on the device in one call: a list of ``h x w`` uint8
+    arrays, the pixels libjpeg decodes.  Raises ``ValueError`` naming the
+    first file that is not decoded and its status (1: a JPEG outside what
+    libjpeg writes for 8-bit grayscale tiles, 2: corrupt)."""
+    parts = [np.frombuffer(f, np.uint8) if isinstance(f, (bytes, bytearray, memoryview))
+             else np.ascontiguousarray(f, dtype=np.uint8).ravel() for f in files]
+    if not parts:
+        return []
+    offsets = np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.int64)
+    tiles, dims, status = decode_jpeg_blob(np.concatenate(parts), offsets)
+    _raise_for_status(status)
+    return [np.ascontiguousarray(tiles[t, :dims[t, 0], :dims[t, 1]]) for t in range(len(parts))]
+
 
 class Pyramid(object):
     """All levels of a layer's pyramid, resident on the device until
     ``close()`` (about 4/3 x 64 KB per base tile).  Level ``z`` is
     ``dimensions[z]`` tiles, level 0 the single top tile, level ``depth - 1``
-    the base."""
+    the base.  ``jpeg_quality``: None, or the quality of the stored pyramid
+    (``build_pyramid``): every level below the base was halved from the JPEG
+    round trip of the level above at that quality."""
 
-    def __init__(self, geometry):
+    def __init__(self, geometry, jpeg_quality=None):
         self.geometry = geometry
+        self.jpeg_quality = None if jpeg_quality is None else int(jpeg_quality)
         self.depth = geometry.depth
         self.dimensions = list(geometry.dimensions)
         self.empty_base_tiles = geometry.get_empty_base_tile_coordinates()
@@ -533,12 +582,42 @@ class Pyramid(object):
         self._check(z)
         return (self._levels[z],) + tuple(self.dimensions[z]) + tuple(self._last[z])
 
-    def encode_level(self, z, quality=95, stream=None):
+    def _quality(self, quality):
+        if quality is None:
+            return 95 if self.jpeg_quality is None else self.jpeg_quality
+        if self.jpeg_quality is not None and int(quality) != self.jpeg_quality:
+            raise ValueError("this pyramid was built from tiles stored at JPEG quality %d, not %d"
+                             % (self.jpeg_quality, int(quality)))
+        return int(quality)
+
+    def decoded_level(self, z, quality=None, stream=None):
+        """Level z as the reference reads it back from its stored files: the
+        JPEG round trip of every tile (``tmh_jpeg_roundtrip_level_device``),
+        stitched into one array like ``level(z)``."""
+        self._check(z)
+        quality = self._quality(quality)
+        L = hip.lib()
+        rows, cols = self.dimensions[z]
+        out = C.c_void_p()
+        hip.check(L.tmh_malloc_device(C.byref(out), rows * cols * TILE_SIZE * TILE_SIZE))
+        try:
+            hip.check(L.tmh_jpeg_roundtrip_level_device(*self.device_level(z), quality, out, stream))
+            tiles = np.empty((rows, cols, TILE_SIZE, TILE_SIZE), dtype=np.uint8)
+            hip.check(L.tmh_memcpy(hip.ptr(tiles), out, tiles.nbytes, 1, stream))
+        finally:
+            L.tmh_free_device(out)
+        return tiles_to_array(tiles, self._last[z][0], self._last[z][1])
+
+    def encode_level(self, z, quality=None, stream=None):
         """Every tile of level z as the JPEG file ``PyramidTile.jpeg_encode``
         (tmlib/image.py:1073-1094) returns for it: an ``EncodedLevel``.  One
         measuring call, one allocation of the exact size, one writing call and
-        one device-to-host copy of the blob."""
+        one device-to-host copy of the blob.  ``quality``: by default the
+        pyramid's ``jpeg_quality``, or 95 when that is None; on a stored
+        pyramid any other quality raises ``ValueError`` (its lower levels
+        were built from files of that quality)."""
         self._check(z)
+        quality = self._quality(quality)
         L = hip.lib()
         level = self.device_level(z)
         n = level[1] * level[2]
@@ -561,11 +640,13 @@ class Pyramid(object):
                     L.tmh_free_device(p)
         return EncodedLevel(blob, offsets, self.dimensions[z])
 
-    def iter_jpeg_tiles(self, quality=95):
+    def iter_jpeg_tiles(self, quality=None):
         """``(z, y, x, bytes)`` of every tile of every level -- the rows of
         the reference's ``channel_layer_tiles`` table without the layer id --
         the base level first, then upward; row-major within a level.  One
-        level is coded at a time, so the host holds one level's blob."""
+        level is coded at a time, so the host holds one level's blob.
+        ``quality``: as for ``encode_level``."""
+        quality = self._quality(quality)
         for z in range(self.depth - 1, -1, -1):
             enc = self.encode_level(z, quality)
             rows, cols = enc.dimensions
@@ -592,9 +673,11 @@ class Pyramid(object):
             pass
 
 
-def _odd_mosaics_on_host(pyr, z):
+def _odd_mosaics_on_host(pyr, z, src=None):
     """Level z's tiles whose mosaic of level z + 1 tiles has an odd side: the
-    device pass left them unwritten; the exact area mean on the host."""
+    device pass left them unwritten; the exact area mean on the host.  ``src``:
+    the device level the source tiles are read from (default: level z + 1
+    itself; the stored pyramid passes its JPEG round trip)."""
     L = hip.lib()
     rows, cols = pyr.dimensions[z]
     src_rows, src_cols = pyr.dimensions[z + 1]
@@ -606,7 +689,7 @@ def _odd_mosaics_on_host(pyr, z):
         mw = sum(pyr.tile_dimensions(z + 1, pre_rows[0], c)[1] for c in pre_cols)
         if mh % 2 == 0 and mw % 2 == 0:
             continue
-        mosaic = np.vstack([np.hstack([pyr.tile(z + 1, r, c).array for c in pre_cols])
+        mosaic = np.vstack([np.hstack([_source_tile(pyr, z + 1, r, c, src) for c in pre_cols])
                             for r in pre_rows])
         half = _area_mean_odd(mosaic)
         full = np.zeros((TILE_SIZE, TILE_SIZE), dtype=np.uint8)
@@ -615,7 +698,17 @@ def _odd_mosaics_on_host(pyr, z):
         hip.check(L.tmh_memcpy(dst, hip.ptr(full), full.nbytes, 0, None))
 
 
-def build_pyramid(geometry, sites_u8, table=None, stream=None):
+def _source_tile(pyr, z, y, x, src):
+    if src is None:
+        return pyr.tile(z, y, x).array
+    h, w = pyr.tile_dimensions(z, y, x)
+    full = np.empty((TILE_SIZE, TILE_SIZE), dtype=np.uint8)
+    at = C.c_void_p(src.value + (y * pyr.dimensions[z][1] + x) * TILE_SIZE * TILE_SIZE)
+    hip.check(hip.lib().tmh_memcpy(hip.ptr(full), at, full.nbytes, 1, None))
+    return np.ascontiguousarray(full[:h, :w])
+
+
+def build_pyramid(geometry, sites_u8, table=None, stream=None, jpeg_quality=None):
     """The pyramid of a layer from its uint8 sites (the chain's output,
     ``Corrector.chain_u8`` / ``tmh_correct_chain_u8_device``).
 
@@ -625,6 +718,14 @@ def build_pyramid(geometry, sites_u8, table=None, stream=None):
     ``plan_base_tiles(geometry)``, when the caller keeps it across layers of
     one geometry (every channel of an experiment).  ``stream``: the
     hipStream_t the sites were produced on (default stream if None).
+    ``jpeg_quality``: None halves the uncoded pixels.  An int builds the
+    layer the reference stores: level z - 1 is the halving of level z's JPEG
+    round trip at that quality (what ``_create_lower_zoom_level_tiles`` reads
+    back through ``ChannelLayerTile.pixels``), at every level, while level z
+    itself stays the uncoded pixels, so that ``encode_level(z)`` writes the
+    stored files.  The round trip goes into one scratch buffer, sized for the
+    base level and freed when the top is done: peak device memory is the
+    pyramid plus one base level.
     Returns a ``Pyramid``; the call returns when it is complete."""
     L = hip.lib()
     if table is None:
@@ -640,7 +741,8 @@ def build_pyramid(geometry, sites_u8, table=None, stream=None):
         staged = C.c_void_p()
         hip.check(L.tmh_malloc_device(C.byref(staged), a.nbytes))
         dev = staged.value
-    pyr = Pyramid(geometry)
+    pyr = Pyramid(geometry, jpeg_quality)
+    scratch = C.c_void_p()
     try:
         if staged is not None:
             hip.check(L.tmh_memcpy(staged, hip.ptr(a), a.nbytes, 0, stream))
@@ -649,19 +751,27 @@ def build_pyramid(geometry, sites_u8, table=None, stream=None):
         hip.check(L.tmh_tiles_base_device(C.c_void_p(dev), n, H, W, hip.ptr(table), len(table),
                                           pyr._alloc(z), rows, cols, stream))
         pyr._last[z] = (TILE_SIZE, TILE_SIZE)
+        if jpeg_quality is not None and z > 0:
+            hip.check(L.tmh_malloc_device(C.byref(scratch), rows * cols * TILE_SIZE * TILE_SIZE))
         while z > 0:
             rows, cols = pyr.dimensions[z]
             if pyr.dimensions[z - 1] != ((rows + 1) // 2, (cols + 1) // 2):
                 raise ValueError("level %d of %r tiles does not halve into %r"
                                  % (z, (rows, cols), pyr.dimensions[z - 1]))
             lh, lw = C.c_int(), C.c_int()
-            hip.check(L.tmh_pyramid_shrink2_device(pyr._levels[z], rows, cols, pyr._last[z][0],
+            src = pyr._levels[z]
+            if jpeg_quality is not None:
+                hip.check(L.tmh_jpeg_roundtrip_level_device(src, rows, cols, pyr._last[z][0],
+                                                            pyr._last[z][1], pyr.jpeg_quality,
+                                                            scratch, stream))
+                src = scratch
+            hip.check(L.tmh_pyramid_shrink2_device(src, rows, cols, pyr._last[z][0],
                                                    pyr._last[z][1], pyr._alloc(z - 1),
                                                    C.byref(lh), C.byref(lw), stream))
             pyr._last[z - 1] = (lh.value, lw.value)
             if pyr._last[z][0] % 2 or pyr._last[z][1] % 2:
                 hip.check(L.tmh_synchronize(stream))
-                _odd_mosaics_on_host(pyr, z - 1)
+                _odd_mosaics_on_host(pyr, z - 1, None if jpeg_quality is None else scratch)
             z -= 1
         hip.check(L.tmh_synchronize(stream))
     except Exception:
@@ -670,4 +780,6 @@ def build_pyramid(geometry, sites_u8, table=None, stream=None):
     finally:
         if staged is not None:
             L.tmh_free_device(staged)
+        if scratch.value:
+            L.tmh_free_device(scratch)
     return pyr
