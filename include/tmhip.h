@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TMH_ABI_VERSION 6
+#define TMH_ABI_VERSION 7
 
 #define TMH_OK 0
 #define TMH_EINVAL (-22)  /* bad argument: maps to ValueError / TypeError */
@@ -566,6 +566,48 @@ int tmh_jpeg_decode_tiles_device(const uint8_t* dev_blob, const int64_t* dev_off
                                  void* stream);
 int tmh_jpeg_decode_tiles(const uint8_t* host_blob, const int64_t* host_offsets, int64_t n,
                           uint8_t* host_tiles, int32_t* host_dims, int32_t* host_status);
+
+/* ---- registration: the align step's shifts ---------------------------------
+ * Replaces tmlib/workflow/align/registration.py:23-86 (calculate_shift, i.e.
+ * image_registration.chi2_shift rounded to integers) for every (target,
+ * reference) pair of a job (tmlib/workflow/align/api.py:157-260).
+ *
+ * For a target T and a reference R of the same shape H x W, from the
+ * mean-removed images (exact integer sums),
+ *     C[dy, dx] = sum_{r,c} T[r, c] * R[(r + dy) mod H, (c + dx) mod W]
+ * and the shift is the argmax of C in signed form: a lag d along an axis of
+ * length L is d when d <= L / 2 (integer division), else d - L.  So (y, x)
+ * means T[r, c] ~ R[r + y, c + x], the sign _shift_and_crop expects.  Ties go
+ * to the lowest flat unsigned lag dy * W + dx; two constant images give (0, 0).
+ * C is computed in f32 by a 2-D FFT; an axis whose length has a prime factor
+ * above 5 is zero-padded to a 5-smooth length >= 2 L - 1 and the linear
+ * correlation folded back to period L.  A transformed line holds at most 4,096
+ * values: an axis is at most 4,096 when 5-smooth and at most 2,048 otherwise
+ * (TMH_EINVAL beyond).
+ *
+ * targets [n][H][W] and references [m][H][W] of elem_bytes 1 (uint8) or 2
+ * (uint16); target i is registered against reference ref_of_target[i] (host,
+ * each in 0..m-1).  y, x (host, n) and peak (host, n, may be NULL: C at the
+ * argmax) are filled when the call returns.  dev_scratch: at least
+ * tmh_register_scratch_bytes(n, m, H, W) bytes, 256-byte aligned (that
+ * function returns a negative code for arguments the calls reject).  Queued on
+ * `stream` (NULL: the default stream).  n = 0 does nothing. */
+int64_t tmh_register_scratch_bytes(int64_t n, int64_t m, int height, int width);
+int tmh_register_shifts_device(const void* dev_targets, int64_t n, const void* dev_refs, int64_t m,
+                               int height, int width, int elem_bytes,
+                               const int32_t* host_ref_of_target, void* dev_scratch,
+                               int64_t scratch_bytes, int32_t* host_y, int32_t* host_x,
+                               float* host_peak, void* stream);
+int tmh_register_shifts(const void* host_targets, int64_t n, const void* host_refs, int64_t m,
+                        int height, int width, int elem_bytes, const int32_t* ref_of_target,
+                        int32_t* y, int32_t* x, float* peak);
+/* The f32 plane C[H][W] of one pair, in unsigned lag order (scratch as for
+ * n = m = 1).  The device form returns when the plane is complete. */
+int tmh_xcorr_plane_device(const void* dev_target, const void* dev_ref, int height, int width,
+                           int elem_bytes, void* dev_scratch, int64_t scratch_bytes,
+                           float* dev_plane, void* stream);
+int tmh_xcorr_plane(const void* host_target, const void* host_ref, int height, int width,
+                    int elem_bytes, float* host_plane);
 
 /* ChannelImage.clip alone (image.py:589), u16. */
 int tmh_clip_u16(const uint16_t* host_in, uint16_t* host_out, int64_t n, int lo, int hi);

@@ -470,6 +470,14 @@ void jpeg_decode_tables_host(void* tables);
 void launch_jpeg_decode_tiles(const uint8_t* blob, const int64_t* offsets, int64_t n,
                               const void* d_tables, uint8_t* tiles, int32_t* dims,
                               int32_t* status, hipStream_t s);
+// Registration (register_kernels.hip): shifts of n targets against their
+// references by FFT cross-correlation; dev_plane (may be NULL): the f32 planes
+// [n][H][W].  Returns when the host outputs are filled.
+int64_t register_scratch_bytes(int64_t n, int64_t m, int H, int W);
+void launch_register(const void* dev_targets, int64_t n, const void* dev_refs, int64_t m, int H,
+                     int W, int elem_bytes, const int32_t* host_ref_of, void* dev_scratch,
+                     int64_t scratch_bytes, int32_t* host_y, int32_t* host_x, float* host_peak,
+                     float* dev_plane, hipStream_t s);
 void launch_clip_u16(const uint16_t* in, uint16_t* out, int64_t n, int lo, int hi, hipStream_t s);
 void launch_synth(uint16_t* out, int64_t n_sites, int H, int W, uint64_t seed, int channel,
                   int64_t first_site, int dist, hipStream_t s);

@@ -33,7 +33,7 @@ TMH_FUSED_NO_HIST = 100
 TMH_SYNTH_STANDARD = 0
 TMH_SYNTH_BRIGHT = 1
 TMH_SYNTH_UNIFORM = 2
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _P = C.c_void_p
 _I64 = C.c_int64
@@ -110,6 +110,12 @@ SIGNATURES = {
     "tmh_jpeg_roundtrip_level": (_I, [_P, _I, _I, _I, _I, _I, _P]),
     "tmh_jpeg_decode_tiles_device": (_I, [_P, _P, _I64, _P, _P, _P, _P]),
     "tmh_jpeg_decode_tiles": (_I, [_P, _P, _I64, _P, _P, _P]),
+    "tmh_register_scratch_bytes": (_I64, [_I64, _I64, _I, _I]),
+    "tmh_register_shifts_device": (_I, [_P, _I64, _P, _I64, _I, _I, _I, _P, _P, _I64, _P, _P, _P,
+                                        _P]),
+    "tmh_register_shifts": (_I, [_P, _I64, _P, _I64, _I, _I, _I, _P, _P, _P, _P]),
+    "tmh_xcorr_plane_device": (_I, [_P, _P, _I, _I, _I, _P, _I64, _P, _P]),
+    "tmh_xcorr_plane": (_I, [_P, _P, _I, _I, _I, _P]),
     "tmh_synth_sites_device": (_I, [_P, _I64, _I, _I, C.c_uint64, _I, _I64, _I, _P]),
     "tmh_synth_tables": (_I, [_I, _I, _I, _P, _P, _P, _P]),
     "tmh_box_probe_device": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I, _P, C.POINTER(_D),
