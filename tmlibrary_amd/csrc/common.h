@@ -240,6 +240,7 @@ struct ZeroList {
   int64_t count[8];  // u64 elements
   int n = 0;
   void add(void* ptr, int64_t elems) {
+    TMH_CHECK(n < 8, TMH_EINVAL, "zero list is full");
     p[n] = static_cast<unsigned long long*>(ptr);
     count[n++] = elems;
   }
@@ -252,6 +253,7 @@ struct ZeroList32 {
   int count[16];  // u32 elements
   int n = 0;
   void add(void* ptr, int elems) {
+    TMH_CHECK(n < 16, TMH_EINVAL, "zero list is full");
     p[n] = static_cast<unsigned int*>(ptr);
     count[n++] = elems;
   }
@@ -259,6 +261,7 @@ struct ZeroList32 {
 void launch_zero_u32(const ZeroList32& z, hipStream_t s);
 
 constexpr int kMaxJobs = 8;          // jobs (a rank's channels) of one multi-job launch
+static_assert(2 * kMaxJobs <= 16, "ZeroList32 holds two arrays per job of a multi-job launch");
 // Several fused jobs' histogram tails (same image size)
 struct TailJob {
   uint32_t* hist;                  // the job's histogram slab (zero-maintained)

@@ -33,7 +33,7 @@ ProfScope::~ProfScope() {}
 }  // namespace tmh
 using namespace tmh;
 
-static std::vector<double> taps5() {  // abi.hip gaussian_taps(5)
+static std::vector<double> taps5() {  // abi_apply.hip gaussian_taps(5)
   const int lw = 20;
   std::vector<double> w(2 * lw + 1, 0.0);
   w[lw] = 1.0;

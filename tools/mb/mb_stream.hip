@@ -260,7 +260,7 @@ int main(int argc, char** argv) {
                          queues);
     };
     // the packed configuration (cfg 5: 4 sites, 1,024 threads, u16 counters,
-    // rare lists), as abi.hip launches it for bright jobs
+    // rare lists), as abi_fused.hip launches it for bright jobs
     auto fusedp = [&](auto kern, int bands) {
       CK(hipMemsetAsync(fn, 0, 4, 0));
       CK(hipMemsetAsync(rmask, 0, S * 8, 0));
