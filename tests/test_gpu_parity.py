@@ -67,12 +67,16 @@ def check_order_stats(sites, got, q=None):
         assert np.array_equal(b, orc.order_statistics_from_hist(hs, hi)), "site %d next" % i
 
 
-def run_stats(sites, log=True, decimals=3, batch=3, flags=0):
+def run_stats(sites, log=True, decimals=3, batch=3, flags=0, after_batch=None):
+    """after_batch(st, i0): called once a full batch (sites[i0:i0 + batch])
+    has been flushed to the GPU, while it is the handle's last batch."""
     from tmlibrary_amd.image import ChannelImage
     from tmlibrary_amd.workflow.corilla.stats import OnlineStatistics
     st = OnlineStatistics(sites[0].shape, decimals=decimals, batch_size=batch, flags=flags)
-    for s in sites:
+    for i, s in enumerate(sites):
         st.update(ChannelImage(np.ascontiguousarray(s)), log_transform=log)
+        if after_batch is not None and (i + 1) % batch == 0:
+            after_batch(st, i + 1 - batch)
     return st
 
 
@@ -779,6 +783,59 @@ def test_order_statistics_scatter_path(L, kind):
     check_order_stats(sites, site_order_stats(L, st._h, range(len(sites)), 100000))
     ref = orc.run_illumstats(sites)
     assert np.array_equal(st.percentile_sums, ref.percentile_sums)
+
+
+# values at the edges of what k_hist_scatter's round mask is derived from:
+# 1,024-bin rounds (0 | 1023, 1024 | 2047), the LDS / slab split (32767 |
+# 32768), a 64-bin bit of himask (32831 | 32832), a 2,048-bin word of himask
+# (34815 | 34816), the last round (64511 | 64512 .. 65535)
+MASK_EDGES = (0, 1023, 1024, 2047, 31743, 32767, 32768, 32831, 32832, 34815, 34816, 64511, 64512,
+              65535)
+
+
+def round_mask_edge_sites(shape):
+    """28 sites: one constant site per edge value, one two-value site per
+    adjacent pair (the first third of the pixels holds the lower value), one
+    site drawn uniformly from the values.  Ordered in batches of 7 that
+    alternate sites with a value >= 32768 (slab counts) and sites without:
+    7 high, 7 low, 7 high, then the 4 low and 3 high that are left -- every
+    slab row is used again after a high site has used it."""
+    n = shape[0] * shape[1]
+    sites = [np.full(shape, v, np.uint16) for v in MASK_EDGES]
+    for a, b in zip(MASK_EDGES[:-1], MASK_EDGES[1:]):
+        s = np.full(n, b, np.uint16)
+        s[:n // 3] = a
+        sites.append(s.reshape(shape))
+    rng = np.random.default_rng(17)
+    sites.append(np.array(MASK_EDGES, np.uint16)[rng.integers(0, len(MASK_EDGES), shape)])
+    high = [s for s in sites if s.max() >= 32768]
+    low = [s for s in sites if s.max() < 32768]
+    assert (len(high), len(low)) == (17, 11)
+    return high[:7] + low[:7] + high[7:14] + low[7:] + high[14:]
+
+
+@pytest.mark.parametrize("shape", [(16, 24), (15, 23)])
+def test_scatter_round_mask_edges(L, shape):
+    """k_hist_scatter's round mask (which 1,024-bin rounds of a site hold
+    counts: the low half from the LDS bins, the high half from himask) at the
+    edges of its derivation, on the 16-byte vector path (384 pixels) and the
+    scalar path (345): every site's order statistics for all 100,000
+    quantiles and its histogram, the percentile sums and the pooled histogram,
+    bit for bit, with the zero-maintained slab reused after high sites."""
+    from tmlibrary_amd import hip
+    sites = round_mask_edge_sites(shape)
+    hists = [orc.histogram_u16(s) for s in sites]
+
+    def check_batch(st, i0):
+        check_order_stats(sites[i0:i0 + 7], site_order_stats(L, st._h, range(7), 100000))
+        for i in range(7):
+            h = np.empty(65536, np.uint32)
+            hip.check(L.tmh_stats_site_histogram(st._h, i, hip.ptr(h)))
+            assert np.array_equal(h.astype(np.uint64), hists[i0 + i]), "site %d histogram" % (i0 + i)
+
+    st = run_stats(sites, batch=7, flags=hip.TMH_STATS_KEEP_SITE_HIST, after_batch=check_batch)
+    assert np.array_equal(st.percentile_sums, orc.run_illumstats(sites).percentile_sums)
+    assert np.array_equal(st.histogram, sum(hists)), "pooled histogram"
 
 
 @pytest.mark.parametrize("qkind", ["linspace", "custom"])

@@ -125,7 +125,7 @@ static void fused_post(FusedPass& p, bool fixed) {
                        c->log_transform, p.clip_lo, p.clip_hi, s, p.tab);
   if (p.cfg == kFusedNoHist)  // the histograms from one more read of the sites
     launch_hist_site_u16(p.in, h->npx, n_sites, h->hist_full.p, h->qp, p.vlh, p.ld, h->pooled.p,
-                         h->pooled_parts.p, kPooledParts, h->zeros.p, p.sh, nullptr, 0, s, p.tab);
+                         h->pooled_parts.p, h->zeros.p, p.sh, s, p.tab);
   // the Welford pass's diagnostic wide counts restart with the next batch
   // (reset here on s, before any later Welford launch on the handle)
   if (h->pending - n_sites == 0) {
@@ -170,14 +170,21 @@ static void fused_tail_end(FusedPass& p, hipStream_t ts) {
   }
 }
 
+// what the histogram tail reads and writes for the job
+static TailJob tail_job(const FusedPass& p) {
+  tmh_stats* h = p.h;
+  QPos qp = h->qp;
+  qp.tstride = p.ld * kOsTile;
+  return TailJob{h->hist_full.p, h->hist_rmask.p,
+                 reinterpret_cast<const unsigned long long*>(p.c->queues.p + 8), qp,
+                 p.vlh, h->pooled.p, h->zeros.p, p.sh, p.n};
+}
+
 // one job's histogram tail, on its handle's tail stream (or s)
 static void fused_tail(FusedPass& p) {
   hipStream_t ts = fused_tail_stream(p);
-  tmh_stats* h = p.h;
   if (p.cfg != kFusedNoHist)  // (very wide: k_hist_site_u16 wrote the order statistics)
-    launch_hist_finalize(h->hist_full.p, h->hist_rmask.p, 0, p.n, h->qp, p.vlh, p.ld, h->pooled.p,
-                         h->pooled_parts.p, kPooledParts, h->zeros.p, p.sh, ts, false,
-                         reinterpret_cast<const unsigned long long*>(p.c->queues.p + 8));
+    launch_hist_finalize(tail_job(p), ts);
   fused_tail_end(p, ts);
 }
 
@@ -352,15 +359,9 @@ static void correct_hist_multi(tmh_corrector* const* cs, tmh_stats* const* hs, i
   }
   hipStream_t ts = fused_tail_stream(p[0]);
   TailJobs T{};
-  for (int j = 0; j < np; ++j) {
-    if (p[j].cfg == kFusedNoHist) continue;  // its order statistics are written
-    tmh_stats* h = p[j].h;
-    QPos qp = h->qp;
-    qp.tstride = p[j].ld * kOsTile;
-    T.j[T.n++] = TailJob{h->hist_full.p, h->hist_rmask.p,
-                         reinterpret_cast<const unsigned long long*>(p[j].c->queues.p + 8), qp,
-                         p[j].vlh, h->pooled.p, h->zeros.p, p[j].sh, p[j].n};
-  }
+  for (int j = 0; j < np; ++j)
+    if (p[j].cfg != kFusedNoHist)  // (very wide: its order statistics are written)
+      T.j[T.n++] = tail_job(p[j]);
   launch_hist_finalize_jobs(T, ts);
   for (int j = 0; j < np; ++j) fused_tail_end(p[j], ts);
 }

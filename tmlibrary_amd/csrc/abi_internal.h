@@ -300,8 +300,6 @@ inline void cross_end(tmh_stats* h, hipStream_t s) {
   defer_join(h, s);
 }
 
-constexpr int kPooledParts = 16;
-
 // what the fused pass and the chain use of the statistics handle
 // (abi_stats.hip) and the corrector (abi_apply.hip)
 size_t os_words(const tmh_stats* h, int64_t n_sites);

@@ -182,7 +182,7 @@ __device__ __forceinline__ int64_t site_in_block(const SiteTab& t, int64_t s) {
   return s & ((1ll << t.shift) - 1);
 }
 
-// bright: 1 = the host's site probe found bright sites (the 16,384-entry LUT
+// bright: 1 = the host's site probe found bright sites (the 20,472-entry LUT
 // pass in three site parts where the launch allows), 0 = standard
 void launch_welford(const uint16_t* sites, int64_t npx, int64_t n_sites, int64_t n0, double* rn,
                     double* mean, double* m2, const double* lut, int log_transform,
@@ -199,21 +199,15 @@ void launch_site_probe(const uint16_t* sites, int64_t npx, int64_t n_sites, unsi
 void launch_hist_scatter(const uint16_t* sites, int64_t npx, int64_t n_sites, uint32_t* hist_hi,
                          const QPos& p, uint32_t* vlh, int64_t vlh_ld, unsigned long long* pooled,
                          int64_t* zero_counts, uint32_t* site_hist, hipStream_t s);
-void launch_hist_finalize(uint32_t* hist, unsigned long long* rmask, int dense_rounds,
-                          int64_t n_sites, const QPos& p, uint32_t* vlh, int64_t vlh_ld,
-                          unsigned long long* pooled,
-                          unsigned long long* pooled_parts, int n_parts, int64_t* zero_counts,
-                          uint32_t* site_hist, hipStream_t s, bool narrow = false,
-                          const unsigned long long* rm_all = nullptr,
-                          const unsigned long long* wide = nullptr, unsigned long long xthr = 0);
 // very wide launches: the exact per-site histogram in LDS as u16 pairs from
-// one more read of the sites, scanned into order statistics (wide == null:
-// unconditionally; else only when wide[1] >= xthr)
+// one more read of the sites, scanned into order statistics; the pooled
+// histogram through pooled_parts, kPooledParts zero-maintained copies of it
+// (workgroups spread their adds over them: fewer same-address collisions)
+constexpr int kPooledParts = 16;
 void launch_hist_site_u16(const uint16_t* sites, int64_t npx, int64_t n_sites, uint32_t* slab,
                           const QPos& p, uint32_t* vlh, int64_t vlh_ld,
                           unsigned long long* pooled, unsigned long long* pooled_parts,
-                          int n_parts, int64_t* zero_counts, uint32_t* site_hist,
-                          const unsigned long long* wide, unsigned long long xthr, hipStream_t s,
+                          int64_t* zero_counts, uint32_t* site_hist, hipStream_t s,
                           const SiteTab& tab = SiteTab{});
 void launch_pct_accumulate(const uint32_t* vlh, int64_t n_sites, int64_t vlh_ld, int Q,
                            const double* gamma, double* acc, hipStream_t s);
@@ -222,11 +216,6 @@ void launch_pct_accumulate_range(const uint32_t* vlh, int64_t n_sites, int64_t v
                                  int q_count, const double* gamma, double* acc, hipStream_t s,
                                  const unsigned long long* only_xwide = nullptr,
                                  unsigned long long xthr = 0);
-// pooled[b] += sum over the sites of hist[s][b] for the rounds rmask names
-// (rm_all: the launch-wide union of the masks, or null)
-void launch_pooled_colsum(const uint32_t* hist, const unsigned long long* rmask,
-                          const unsigned long long* rm_all, int64_t n_sites,
-                          unsigned long long* pooled, hipStream_t s);
 void launch_finalize(const double* mean, const double* m2, int64_t n, int64_t npx, double* out_mean,
                      double* out_std, hipStream_t s);
 // var = M2 / (n - 1), NaN where n < 2 (stats.py:94-102)
@@ -262,11 +251,13 @@ void launch_zero_u32(const ZeroList32& z, hipStream_t s);
 
 constexpr int kMaxJobs = 8;          // jobs (a rank's channels) of one multi-job launch
 static_assert(2 * kMaxJobs <= 16, "ZeroList32 holds two arrays per job of a multi-job launch");
-// Several fused jobs' histogram tails (same image size)
+// Fused jobs' histogram tails: per job the pooled histogram (a column sum of
+// the sites' histograms over the rounds the masks name) and every site's
+// order statistics, in two launches for all the jobs
 struct TailJob {
   uint32_t* hist;                  // the job's histogram slab (zero-maintained)
   unsigned long long* rmask;       // per site: rounds holding counts (zero-maintained)
-  const unsigned long long* rm_all;  // the union of the masks
+  const unsigned long long* rm_all;  // the union of the masks, or null
   QPos qp;                         // the handle's quantile table (tstride set)
   uint32_t* vlh;                   // order statistics of the job's first site
   unsigned long long* pooled;
@@ -279,6 +270,7 @@ struct TailJobs {
   int n;
 };
 void launch_hist_finalize_jobs(const TailJobs& J, hipStream_t s);
+void launch_hist_finalize(const TailJob& job, hipStream_t s);  // one job
 constexpr int kMaxPlanes = 2 * kMaxJobs;
 void launch_smooth(const double* in, double* out, double* tmp, int H, int W, const double* d_w,
                    int radius, hipStream_t s);

@@ -1,7 +1,10 @@
-// Order statistics of one site's histogram (np.percentile 'linear' previous /
-// next sorted values, tmlib/workflow/corilla/stats.py:75-76) written from its
-// counts: shared by the standalone finalize kernels (stats_kernels.hip) and
-// the fused pass's in-pass finalize (fused_kernels.hip).
+// The histogram tail: one site's 65,536 counts -> its order statistics
+// (np.percentile 'linear' previous / next sorted values,
+// tmlib/workflow/corilla/stats.py:75-76), pooled-histogram adds, zero count and
+// debug histogram copy.  Included by stats_kernels.hip only; hist_tail_rounds
+// is the one walker behind its three users: k_hist_scatter (counts in LDS and
+// a global slab), k_hist_finalize (the fused pass's global histograms) and
+// k_hist_site_u16 (u16 pairs in LDS).
 #pragma once
 
 #include "common.h"
@@ -37,14 +40,8 @@ __device__ __forceinline__ uint32_t block_exscan_t(uint32_t c, uint32_t* slots, 
   return woff + incl - c;
 }
 
-__device__ __forceinline__ uint32_t block_exscan(uint32_t c, uint32_t* slots, int round,
-                                                 uint32_t* total) {
-  return block_exscan_t<kHistThreads>(c, slots, round, total);
-}
-
 constexpr int kRound = 1024;  // histogram bins per round of the scans
 
-constexpr int kTailChunkDefault = 8;  // rounds whose counts are loaded together
 // Advance (t, Rt = R[t]) to the first index >= t with R[index] > x (R: LEN
 // non-decreasing inclusive prefix ranks in LDS; the caller guarantees
 // R[t - 1] <= x < R[LEN - 1]).  Consecutive quantile positions mostly stay in
@@ -87,7 +84,7 @@ __device__ __forceinline__ void advance_rank(const int32_t* R, int& t, int32_t& 
 // range is [r0 * scale, r1 * scale] up to rounding (and one position's worth
 // of quantiles), so the groups scanned carry a margin and the position test
 // decides membership exactly.
-template <int NT = kHistThreads, int LEN = kRound>
+template <int NT, int LEN>
 __device__ __forceinline__ void fill_groups(const int32_t* R, int64_t r0, int64_t r1,
                                             uint32_t bin0, const QPos& p,
                                             uint32_t* __restrict__ vlh, bool vec16) {
@@ -172,16 +169,21 @@ __device__ __forceinline__ void fill_groups(const int32_t* R, int64_t r0, int64_
   }
 }
 
-// hist_tail for a histogram whose possibly non-empty 1,024-bin rounds are
-// known up front (need: bit j = round j): only those rounds are loaded, and
-// they are scanned SR rounds at a time (a super-round of SR * 1,024 bins: one
-// block scan and one rank table per super-round that holds any needed round,
-// bins of the rounds not needed taken as 0 without a load) -- BPT = SR *
-// 1024 / NT consecutive bins per thread, the next super-round's counts in
-// flight while the current one is scanned -- instead of walking all 64
-// rounds.  Same outputs as hist_tail (site_hist rows are zero-filled for the
-// rounds not visited).  NT = 256, SR = 1 is the narrow form that fits beside
-// the fused pass's workgroups on a CU.  starts: 2 * SR * 1024 int32 of LDS.
+// Walk a site's histogram in rounds of 1,024 bins.  need: bit j = round j may
+// hold counts; the other rounds are known empty and are not loaded.  The
+// needed rounds are scanned SR at a time (a super-round of SR * 1,024 bins:
+// one block scan and one rank table per super-round that holds a needed round,
+// bins of its rounds not needed taken as 0 without a load) -- BPT = SR * 1024
+// / NT consecutive bins per thread, the next super-round's counts in flight
+// while the current one is scanned.  count(b) returns the site's count of
+// value b and is called exactly once per bin of a needed round; done(b, c) is
+// called once per such bin after its count has been used (e.g. to reset it).
+// Writes the site's order statistics, zero_counts[s] and, where given, its
+// pooled-histogram adds and site_hist row (zero-filled for the rounds not
+// visited).  slots: 32 words of LDS; starts: 2 * SR * 1024 int32 of LDS
+// (inclusive prefix ranks, double-buffered by scan).
+// ABL (development ablation, tools/mb; 0 in production): 1 = no order-
+// statistic output.
 template <int ABL, int NT, int SR, typename CountFn, typename DoneFn>
 __device__ __forceinline__ void hist_tail_rounds(unsigned long long need, CountFn count,
                                                  DoneFn done, int64_t s, const QPos& p,
@@ -249,7 +251,7 @@ __device__ __forceinline__ void hist_tail_rounds(unsigned long long need, CountF
     base += total;
 #pragma unroll
     for (int i = 0; i < BPT; ++i)
-      if (c[i] && !(ABL & 4) && pooled) atomicAdd(&pooled[b0 + i], (unsigned long long)c[i]);
+      if (c[i] && pooled) atomicAdd(&pooled[b0 + i], (unsigned long long)c[i]);
     if (ABL & 1) continue;
 #pragma unroll
     for (int i = 0; i < BPT; ++i) R[tid * BPT + i] = (int32_t)(r + inc[i]);

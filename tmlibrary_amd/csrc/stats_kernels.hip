@@ -564,11 +564,12 @@ void launch_site_probe(const uint16_t* sites, int64_t npx, int64_t n_sites, unsi
 // shape = -1: production (kWfThreads, kWfInv); 0..8: (256|512 threads) x
 // (f64 Newton | f64 LDS-table reciprocal | f32 small term) x pipeline depth,
 // for the microbenchmark.  bright (production shape, log transform, no forced
-// split): the host's site probe found bright sites -- the 16,384-entry LUT
-// pass in kWfBrightParts site parts (the log10 pass is VALU-bound there:
-// three times the workgroups even the dispatch rounds, 11.3 vs 12.4 ms with
-// the 4,096-entry pass, profiles/r2/mb_welford_bright_r2za.txt; the 16,384
-// entries 8.0 vs 11.4 ms, profiles/r3/ab_welford_bright16k_bright_r3m.jsonl).
+// split): the host's site probe found bright sites -- the kWfLutBright-entry
+// (20,472: 160 KB) LUT pass in kWfBrightParts site parts (the log10 pass is
+// VALU-bound there: three times the workgroups even the dispatch rounds, 11.3
+// vs 12.4 ms with the 4,096-entry pass, profiles/r2/mb_welford_bright_r2za.txt;
+// round 3's 16,384 entries 8.0 vs 11.4 ms,
+// profiles/r3/ab_welford_bright16k_bright_r3m.jsonl).
 void launch_welford(const uint16_t* sites, int64_t npx, int64_t n_sites, int64_t n0, double* rn,
                     double* mean, double* m2, const double* lut, int log_transform,
                     double* part, size_t part_cap, int forced_parts,
@@ -656,77 +657,9 @@ __device__ __forceinline__ void count8(const uint4 v, uint32_t* bins, uint32_t* 
   }
 }
 
-
-// Walk the 65,536 bins in 64 rounds of 1024 consecutive bins, thread t
-// owning bin 1024*j + t: reads are conflict-free/coalesced, and the dense part
-// of a microscopy histogram (a few thousand adjacent values) is spread over
-// every thread.  count(b) returns the site's count of value b.  Counts are
-// fetched kTailChunk rounds at a time (the next chunk's loads in flight while
-// the current one is scanned) and rounds that are empty for the whole
-// workgroup are skipped, so a typical microscopy site (values < ~10,000 plus
-// saturation) scans ~12 rounds.  `cmask` is 3 words of LDS (chunk masks,
-// triple-buffered), `starts` 2 x 1024 int32 of LDS (per-bin inclusive prefix
-// ranks, double-buffered by round).  done(b, c) is called once per bin
-// after its count has been used (e.g. to reset it).
-// ABL (development ablations, tools/mb; 0 in production): 1 = no order-
-// statistic output, 4 = no pooled histogram adds
-template <int ABL = 0, int kTailChunk = kTailChunkDefault, typename CountFn, typename DoneFn>
-__device__ __forceinline__ void hist_tail(CountFn count, DoneFn done, int64_t s, const QPos& p,
-                                          uint32_t* __restrict__ vlh_all,
-                                          unsigned long long* __restrict__ pooled,
-                                          int64_t* __restrict__ zero_counts,
-                                          uint32_t* __restrict__ site_hist, uint32_t* slots,
-                                          uint32_t* cmask, int32_t* starts) {
-  const int tid = threadIdx.x;
-  uint32_t* vlh = vlh_all + s * (int64_t)kOsTile;  // this site's column of the tiles
-  const bool vec16 = (p.Q & 7) == 0;
-  int64_t base = 0;          // exclusive rank of the current round's first bin
-  int nscan = 0;
-  uint32_t cn[kTailChunk];
-#pragma unroll
-  for (int k = 0; k < kTailChunk; ++k) cn[k] = count((uint32_t)k * kHistThreads + tid);
-  for (int jc = 0; jc < kBins / kHistThreads; jc += kTailChunk) {
-    uint32_t c[kTailChunk];
-#pragma unroll
-    for (int k = 0; k < kTailChunk; ++k) c[k] = cn[k];
-    if (jc + kTailChunk < kBins / kHistThreads) {
-#pragma unroll
-      for (int k = 0; k < kTailChunk; ++k)
-        cn[k] = count((uint32_t)(jc + kTailChunk + k) * kHistThreads + tid);
-    }
-    uint32_t m = 0;
-#pragma unroll
-    for (int k = 0; k < kTailChunk; ++k) m |= (c[k] != 0u ? 1u : 0u) << k;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m |= (uint32_t)__shfl_xor((int)m, off, 64);
-    const int slot = (jc / kTailChunk) % 3;
-    if (tid == 0) cmask[(slot + 1) % 3] = 0u;
-    if ((tid & 63) == 0 && m) atomicOr(&cmask[slot], m);
-    __syncthreads();
-    const uint32_t mask = cmask[slot];
-#pragma unroll
-    for (int k = 0; k < kTailChunk; ++k) {
-      const uint32_t b = (uint32_t)(jc + k) * kHistThreads + tid;
-      if (site_hist) site_hist[s * kBins + b] = c[k];
-      if (b == 0 && zero_counts) zero_counts[s] = c[k];
-      done(b, c[k]);
-      if (!((mask >> k) & 1u)) continue;  // uniform: no counts in this round
-      uint32_t total;
-      const int64_t r = base + block_exscan(c[k], slots, nscan, &total);
-      int32_t* R = starts + (nscan & 1) * kHistThreads;
-      ++nscan;
-      const int64_t r0 = base;
-      base += total;
-      if (c[k] && !(ABL & 4)) atomicAdd(&pooled[b], (unsigned long long)c[k]);
-      if (ABL & 1) continue;
-      R[tid] = (int32_t)(r + c[k]);
-      __syncthreads();  // R visible; the other R buffer is rewritten only after the next scan
-      fill_groups(R, r0, base, (uint32_t)(jc + k) * kHistThreads, p, vlh, vec16);
-    }
-  }
-}
-
-
+// One workgroup per site: counts in LDS (and the slab), then the site's
+// non-empty 1,024-bin rounds as a mask, then the tail over those rounds (a
+// typical microscopy site -- values < ~10,000 plus saturation -- scans ~12).
 __global__ __launch_bounds__(kHistThreads) void k_hist_scatter(
     const uint16_t* __restrict__ sites, int64_t npx, int vec, uint32_t* __restrict__ hist_hi,
     const QPos p, uint32_t* __restrict__ vlh_all,
@@ -735,15 +668,15 @@ __global__ __launch_bounds__(kHistThreads) void k_hist_scatter(
   __shared__ __attribute__((aligned(16))) uint32_t bins[kLdsBins];
   __shared__ uint32_t himask[16];
   __shared__ uint32_t slots[32];
-  __shared__ uint32_t cmask[3];
-  __shared__ int32_t starts[2 * kHistThreads];
+  __shared__ int32_t starts[2 * kRound];
+  __shared__ unsigned long long need;  // the site's rounds that hold counts
   const int tid = threadIdx.x;
   const int64_t s = blockIdx.x;
 
   for (int i = tid; i < kLdsBins / 4; i += kHistThreads)
     reinterpret_cast<uint4*>(bins)[i] = make_uint4(0u, 0u, 0u, 0u);
   if (tid < 16) himask[tid] = 0u;
-  if (tid < 3) cmask[tid] = 0u;
+  if (tid == 0) need = 0ull;
   __syncthreads();
 
   const uint16_t* site = sites + s * npx;
@@ -774,161 +707,141 @@ __global__ __launch_bounds__(kHistThreads) void k_hist_scatter(
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  hist_tail(
+  // Rounds 0..31 from the LDS bins (thread t reads bin t of every round:
+  // conflict-free); rounds 32..63 from himask, whose word w covers bins
+  // kLdsBins + 2,048 w .. in 64-bin bits: bits 0..15 = round 32 + 2 w, bits
+  // 16..31 = round 33 + 2 w.  Each wave's first lane adds the wave's low word
+  // and one himask word.
+  static_assert(kRound == kHistThreads && kHistThreads / 64 == 16 && kLdsBins == 32 * kRound &&
+                    kHiBins == 16 * 2048,
+                "one thread per bin of a round, one wave per himask word");
+  uint32_t lo = 0u;
+#pragma unroll
+  for (int j = 0; j < kLdsBins / kRound; ++j) lo |= (bins[j * kRound + tid] != 0u ? 1u : 0u) << j;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) lo |= (uint32_t)__shfl_xor((int)lo, off, 64);
+  if ((tid & 63) == 0) {
+    const int w = tid >> 6;
+    const uint32_t hm = himask[w];
+    const unsigned long long m = (unsigned long long)lo |
+                                 ((hm & 0xFFFFu) ? 1ull << (32 + 2 * w) : 0ull) |
+                                 ((hm >> 16) ? 1ull << (33 + 2 * w) : 0ull);
+    if (m) atomicOr(&need, m);
+  }
+  __syncthreads();
+
+  // SR = 1: 8 KB of ranks beside the 128 KB of bins.  Every slab bin that was
+  // added to lies in a round whose himask bit is set, so it is read and reset.
+  hist_tail_rounds<0, kHistThreads, 1>(
+      need,
       [&](uint32_t b) -> uint32_t {
         if (b < (uint32_t)kLdsBins) return bins[b];
         const uint32_t h = b - kLdsBins;
         return ((himask[h >> 11] >> ((h >> 6) & 31u)) & 1u) ? atomicExch(&hhi[h], 0u) : 0u;
       },
       [](uint32_t, uint32_t) {},
-      s, p, vlh_all, pooled, zero_counts, site_hist, slots, cmask, starts);
+      s, p, vlh_all, pooled, zero_counts, site_hist, slots, starts);
 }
 
-// Per-site histogram (65,536 counts, exact) -> order statistics, written from
-// a complete histogram held in global memory (zero-maintained: every count is
-// read and reset), e.g. accumulated by the fused correct+histogram pass.
-// ABL 8: counts are not reset (re-runnable).  NT threads per site (1024, or
-// 256: one workgroup fits beside the fused pass's two on a CU -- VGPRs <= 64).
-// rmask (may be NULL: every round is read): per site, the 1,024-bin rounds
-// at or above dense_rounds that hold counts; the others are known empty and
-// are not read (a microscopy site touches a handful of the 64).  The mask is
-// zero-maintained like the counts.
-// super-round width of the finalize: 8 rounds (8,192 bins, 32 KB of ranks
-// per buffer) for the 1,024-thread form, 1 for the narrow side-stream form.
-// Round 6: 8 instead of 4 -- bright sites (45 of 64 rounds in use) scan in 6
-// super-rounds instead of 12: bright job 136.1k / 136.7k vs 135.5k / 134.5k,
-// standard 166.9k / 165.4k vs 166.5k / 166.6k, same box ABBA
-// (profiles/r6/ab_finalize_sr8_*_r6g.jsonl).
-template <int NT>
-struct FinSR {
-  static constexpr int value = NT >= 1024 ? 8 : 1;
-};
+// The fused pass's histogram tail.  The pass leaves every site's complete
+// histogram (65,536 exact counts) in its job's global slab and, per site, a
+// mask of the 1,024-bin rounds that hold counts (a microscopy site touches a
+// handful of the 64); the other rounds are known empty and are not read.
+// Slab and masks are zero-maintained: what the tail reads, it resets.  Two
+// launches serve any number of jobs (TailJobs; one job is n = 1): the pooled
+// histograms as column sums, then every site's order statistics.
 
-template <int ABL, int NT>
-__device__ __forceinline__ void hist_finalize_site(
-    int64_t s, uint32_t* __restrict__ hist, unsigned long long* __restrict__ rmask,
-    int dense_rounds, const QPos& p, uint32_t* __restrict__ vlh_all,
-    unsigned long long* __restrict__ pooled, int n_pooled, int64_t* __restrict__ zero_counts,
-    uint32_t* __restrict__ site_hist) {
-  constexpr int SR = FinSR<NT>::value;
-  __shared__ uint32_t slots[32];
-  __shared__ int32_t starts[2 * SR * kRound];
-  const unsigned long long rm = rmask ? rmask[s] : ~0ull;
-  __syncthreads();
-  if (rmask && !(ABL & 8) && threadIdx.x == 0) rmask[s] = 0ull;  // every thread has read it
-  uint32_t* h = hist + s * (int64_t)kBins;
-  // sites spread their pooled-histogram adds over n_pooled copies (fewer
-  // same-address atomic collisions); k_pooled_fold sums the copies
-  unsigned long long* pl = pooled ? pooled + (int64_t)(s % n_pooled) * kBins : nullptr;
-  const unsigned long long dense = dense_rounds >= 64 ? ~0ull : ((1ull << dense_rounds) - 1ull);
-  hist_tail_rounds<ABL & 7, NT, SR>(
-      dense | rm, [&](uint32_t b) -> uint32_t { return h[b]; },
-      [&](uint32_t b, uint32_t c) {
-        if (!(ABL & 8) && c) h[b] = 0u;
-      },
-      s, p, vlh_all, pl, zero_counts, site_hist, slots, starts);
-}
-
-template <int ABL = 0, int NT = kHistThreads>
-__global__ __launch_bounds__(NT, 8) void k_hist_finalize(
-    uint32_t* __restrict__ hist, unsigned long long* __restrict__ rmask, int dense_rounds,
-    const QPos p, uint32_t* __restrict__ vlh_all,
-    unsigned long long* __restrict__ pooled, int n_pooled,
-    int64_t* __restrict__ zero_counts, uint32_t* __restrict__ site_hist,
-    const unsigned long long* __restrict__ wide = nullptr, unsigned long long xthr = 0) {
-  // a very wide launch: k_hist_site_u16 has written this site's outputs
-  if (wide && __builtin_nontemporal_load(wide + 1) >= xthr) return;
-  hist_finalize_site<ABL, NT>(blockIdx.x, hist, rmask, dense_rounds, p, vlh_all, pooled, n_pooled,
-                              zero_counts, site_hist);
-}
-
-// Several jobs' finalize in one launch (blockIdx.y = job): each site's order
-// statistics from its job's histogram slab and round mask (the pooled
-// histograms come from the column sum)
-__global__ __launch_bounds__(kHistThreads, 8) void k_hist_finalize_jobs(const TailJobs J) {
-  const TailJob& t = J.j[blockIdx.y];
-  if ((int64_t)blockIdx.x >= t.n_sites) return;  // uniform per workgroup
-  hist_finalize_site<0, kHistThreads>(blockIdx.x, t.hist, t.rmask, 0, t.qp, t.vlh, nullptr, 1,
-                                      t.zero_counts, t.site_hist);
-}
-
-// Pooled histogram of a fused launch's sites without per-site atomics:
-// pooled[b] += sum over the sites of hist[s][b], read only where site s's
-// round mask names b's 1,024-bin round (the other rounds are known empty).
-// Thread = bin, blockIdx.y = a chunk of kColSites sites: coalesced 1 KB rows,
-// one 64-bit atomic per bin and chunk.  Runs before k_hist_finalize, which
-// reads and resets the same counts; on bright sites (45 of 64 rounds in use)
-// this replaced ~30,000 per-site atomics per site in the finalize (1.2 ms of
-// its 2.4 ms at 3,456 sites: profiles/r2/mb_tail_bright_r2y.txt).
+// Pooled histogram of a job's sites without per-site atomics: pooled[b] +=
+// sum over the sites of hist[s][b], read only where site s's round mask names
+// b's round.  Thread = bin, blockIdx.y = a chunk of kColSites sites,
+// blockIdx.z = job: coalesced 1 KB rows, one 64-bit atomic per bin and chunk.
+// Runs before k_hist_finalize, which reads and resets the same counts; on
+// bright sites (45 of 64 rounds in use) this replaced ~30,000 per-site atomics
+// per site in the finalize (1.2 ms of its 2.4 ms at 3,456 sites:
+// profiles/r2/mb_tail_bright_r2y.txt).
 constexpr int kColSites = 32;
-__device__ __forceinline__ void pooled_colsum_chunk(const uint32_t* __restrict__ hist,
-                                                    const unsigned long long* __restrict__ rmask,
-                                                    const unsigned long long* __restrict__ rm_all,
-                                                    int64_t n_sites,
-                                                    unsigned long long* __restrict__ pooled) {
+__global__ __launch_bounds__(256) void k_pooled_colsum(const TailJobs J) {
   static_assert(kColSites <= 256, "one mask per thread");
+  const TailJob& t = J.j[blockIdx.z];
+  const int64_t s0 = (int64_t)blockIdx.y * kColSites;
+  if (s0 >= t.n_sites) return;  // uniform per workgroup
   __shared__ uint32_t use[kColSites];  // per site of the chunk: this round holds counts
   __shared__ int any;
   const int b = (int)blockIdx.x * 256 + threadIdx.x;
   const int round = (int)blockIdx.x >> 2;  // 256 bins per workgroup, 4 workgroups per round
   // rounds no site of the launch uses (the fused pass's union of the masks)
-  if (rm_all && !((*rm_all >> round) & 1ull)) return;
-  const int64_t s0 = (int64_t)blockIdx.y * kColSites;
-  const int ns = (int)(n_sites - s0 < kColSites ? n_sites - s0 : kColSites);
+  if (t.rm_all && !((*t.rm_all >> round) & 1ull)) return;
+  const int ns = (int)(t.n_sites - s0 < kColSites ? t.n_sites - s0 : kColSites);
   if (threadIdx.x == 0) any = 0;
   __syncthreads();
   if ((int)threadIdx.x < kColSites) {
-    const uint32_t u = (int)threadIdx.x < ns ? (uint32_t)((rmask[s0 + threadIdx.x] >> round) & 1ull) : 0u;
+    const uint32_t u =
+        (int)threadIdx.x < ns ? (uint32_t)((t.rmask[s0 + threadIdx.x] >> round) & 1ull) : 0u;
     use[threadIdx.x] = u;
     if (u) any = 1;
   }
   __syncthreads();
   if (!any) return;  // uniform: no site of the chunk uses this round
-  const uint32_t* h = hist + s0 * kBins + b;
-  unsigned long long t = 0;
+  const uint32_t* h = t.hist + s0 * kBins + b;
+  unsigned long long sum = 0;
 #pragma unroll 16
   for (int s = 0; s < ns; ++s)
-    if (use[s]) t += h[(int64_t)s * kBins];
-  if (t) atomicAdd(&pooled[b], t);
+    if (use[s]) sum += h[(int64_t)s * kBins];
+  if (sum) atomicAdd(&t.pooled[b], sum);
 }
 
-__global__ __launch_bounds__(256) void k_pooled_colsum(const uint32_t* __restrict__ hist,
-                                                       const unsigned long long* __restrict__ rmask,
-                                                       const unsigned long long* __restrict__ rm_all,
-                                                       int64_t n_sites,
-                                                       unsigned long long* __restrict__ pooled) {
-  pooled_colsum_chunk(hist, rmask, rm_all, n_sites, pooled);
+// Each site's order statistics from its job's slab and round mask: blockIdx.x
+// = site, blockIdx.y = job, 1,024 threads scanning the flagged rounds in
+// super-rounds of kFinSuper x 1,024 bins (32 KB of ranks per buffer).  Round
+// 6: 8 instead of 4 -- bright sites (45 of 64 rounds in use) scan in 6 super-
+// rounds instead of 12: bright job 136.1k / 136.7k vs 135.5k / 134.5k, standard
+// 166.9k / 165.4k vs 166.5k / 166.6k, same box ABBA
+// (profiles/r6/ab_finalize_sr8_*_r6g.jsonl).
+// ABL (development ablations, tools/mb; 0 in production): 1 = no order-
+// statistic output, 8 = counts and masks are not reset (re-runnable).
+constexpr int kFinSuper = 8;
+template <int ABL = 0>
+__global__ __launch_bounds__(kHistThreads, 8) void k_hist_finalize(const TailJobs J) {
+  const TailJob& t = J.j[blockIdx.y];
+  const int64_t s = blockIdx.x;
+  if (s >= t.n_sites) return;  // uniform per workgroup
+  __shared__ uint32_t slots[32];
+  __shared__ int32_t starts[2 * kFinSuper * kRound];
+  const unsigned long long rm = t.rmask[s];
+  __syncthreads();
+  if (!(ABL & 8) && threadIdx.x == 0) t.rmask[s] = 0ull;  // every thread has read it
+  uint32_t* h = t.hist + s * (int64_t)kBins;
+  hist_tail_rounds<ABL & 1, kHistThreads, kFinSuper>(
+      rm, [&](uint32_t b) -> uint32_t { return h[b]; },
+      [&](uint32_t b, uint32_t c) {
+        if (!(ABL & 8) && c) h[b] = 0u;
+      },
+      s, t.qp, t.vlh, nullptr, t.zero_counts, t.site_hist, slots, starts);
 }
 
-// blockIdx.z = job (TailJobs)
-__global__ __launch_bounds__(256) void k_pooled_colsum_jobs(const TailJobs J) {
-  const TailJob& t = J.j[blockIdx.z];
-  if ((int64_t)blockIdx.y * kColSites >= t.n_sites) return;  // uniform per workgroup
-  pooled_colsum_chunk(t.hist, t.rmask, t.rm_all, t.n_sites, t.pooled);
-}
-
-// Several fused jobs' histogram tails (pooled column sums, then every site's
-// order statistics) in two launches
 void launch_hist_finalize_jobs(const TailJobs& J, hipStream_t s) {
-  if (J.n <= 0) return;
-  ProfScope prof("hist_finalize", s);
   int64_t nmax = 0;
   for (int j = 0; j < J.n; ++j) nmax = std::max(nmax, J.j[j].n_sites);
   if (nmax <= 0) return;
-  hipLaunchKernelGGL(k_pooled_colsum_jobs,
+  ProfScope prof("hist_finalize", s);
+  hipLaunchKernelGGL(k_pooled_colsum,
                      dim3(kBins / 256, (unsigned)cdiv(nmax, kColSites), (unsigned)J.n), dim3(256), 0,
                      s, J);
-  hipLaunchKernelGGL(k_hist_finalize_jobs, dim3((unsigned)nmax, (unsigned)J.n), dim3(kHistThreads),
+  hipLaunchKernelGGL(k_hist_finalize<0>, dim3((unsigned)nmax, (unsigned)J.n), dim3(kHistThreads),
                      0, s, J);
   TMH_HIP(hipGetLastError());
 }
 
+void launch_hist_finalize(const TailJob& job, hipStream_t s) {
+  TailJobs J{};
+  J.j[0] = job;
+  J.n = 1;
+  launch_hist_finalize_jobs(J, s);
+}
+
 // pooled[b] += sum of the copies; copies reset to zero (zero-maintained)
 __global__ void k_pooled_fold(unsigned long long* __restrict__ pooled,
-                              unsigned long long* __restrict__ parts, int n_parts,
-                              const unsigned long long* __restrict__ wide = nullptr,
-                              unsigned long long xthr = 0) {
-  if (wide && __builtin_nontemporal_load(wide + 1) < xthr) return;  // nothing was added
+                              unsigned long long* __restrict__ parts, int n_parts) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= kBins) return;
   unsigned long long t = 0;
@@ -937,47 +850,6 @@ __global__ void k_pooled_fold(unsigned long long* __restrict__ pooled,
     parts[(int64_t)i * kBins + b] = 0ull;
   }
   pooled[b] += t;
-}
-
-void launch_pooled_colsum(const uint32_t* hist, const unsigned long long* rmask,
-                          const unsigned long long* rm_all, int64_t n_sites,
-                          unsigned long long* pooled, hipStream_t s) {
-  if (n_sites <= 0) return;
-  hipLaunchKernelGGL(k_pooled_colsum, dim3(kBins / 256, (unsigned)cdiv(n_sites, kColSites)),
-                     dim3(256), 0, s, hist, rmask, rm_all, n_sites, pooled);
-  TMH_HIP(hipGetLastError());
-}
-
-void launch_hist_finalize(uint32_t* hist, unsigned long long* rmask, int dense_rounds,
-                          int64_t n_sites, const QPos& p, uint32_t* vlh, int64_t vlh_ld,
-                          unsigned long long* pooled,
-                          unsigned long long* pooled_parts, int n_parts, int64_t* zero_counts,
-                          uint32_t* site_hist, hipStream_t s, bool narrow,
-                          const unsigned long long* rm_all, const unsigned long long* wide,
-                          unsigned long long xthr) {
-  if (n_sites <= 0) return;
-  ProfScope prof(narrow ? "hist_finalize_side" : "hist_finalize", s);
-  QPos pp = p;
-  pp.tstride = vlh_ld * kOsTile;
-  // with a round mask the pooled histogram is a column sum ahead of the
-  // finalize; without one, the finalize adds into pooled copies, then folded
-  const bool colsum = rmask != nullptr && dense_rounds == 0;
-  if (colsum)
-    hipLaunchKernelGGL(k_pooled_colsum, dim3(kBins / 256, (unsigned)cdiv(n_sites, kColSites)),
-                       dim3(256), 0, s, hist, rmask, rm_all, n_sites, pooled);
-  unsigned long long* fin_pooled = colsum ? nullptr : pooled_parts;
-  if (narrow)
-    hipLaunchKernelGGL((k_hist_finalize<0, 256>), dim3((unsigned)n_sites), dim3(256), 0, s, hist,
-                       rmask, dense_rounds, pp, vlh, fin_pooled, n_parts, zero_counts, site_hist,
-                       wide, xthr);
-  else
-    hipLaunchKernelGGL((k_hist_finalize<0, kHistThreads>), dim3((unsigned)n_sites),
-                       dim3(kHistThreads), 0, s, hist, rmask, dense_rounds, pp, vlh, fin_pooled,
-                       n_parts, zero_counts, site_hist, wide, xthr);
-  if (!colsum)
-    hipLaunchKernelGGL(k_pooled_fold, dim3(kBins / 256), dim3(256), 0, s, pooled, pooled_parts,
-                       n_parts);
-  TMH_HIP(hipGetLastError());
 }
 
 // Very wide sites (a third or more of the 8-pixel groups hold a value >=
@@ -997,24 +869,21 @@ void launch_hist_finalize(uint32_t* hist, unsigned long long* rmask, int dense_r
 // workgroup has outstanding at once.  (Spilling at the wrap itself raced: a carry
 // into the upper half, not yet undone, could make an add to the upper half
 // see -- and spill -- a wrap that was not there.)  Launched when the job's
-// site probe finds very wide sites (wide == null), or gated on a count.
+// site probe finds very wide sites.
 constexpr int kU16Threads = 1024;
 constexpr uint32_t kU16Spill = 0x4000u;
 __global__ __launch_bounds__(kU16Threads) void k_hist_site_u16(
     const uint16_t* __restrict__ sites, int64_t npx, int64_t n_sites,
     uint32_t* __restrict__ slab, const QPos p,
     uint32_t* __restrict__ vlh_all, unsigned long long* __restrict__ pooled, int n_pooled,
-    int64_t* __restrict__ zero_counts, uint32_t* __restrict__ site_hist,
-    const unsigned long long* __restrict__ wide, unsigned long long xthr, const SiteTab tab) {
-  if (wide && __builtin_nontemporal_load(wide + 1) < xthr) return;  // uniform: not very wide
+    int64_t* __restrict__ zero_counts, uint32_t* __restrict__ site_hist, const SiteTab tab) {
   constexpr int SR = 2;  // 2,048-bin super-rounds: 16 KB of ranks beside the 128 KB histogram
   __shared__ __attribute__((aligned(16))) uint32_t w16[kBins / 2];
   __shared__ uint32_t slots[32];
   __shared__ int32_t starts[2 * SR * kRound];
   __shared__ unsigned long long ovf;  // rounds with counts in the slab
   const int tid = threadIdx.x;
-  // persistent over the sites (one workgroup per CU fits): a launch that is
-  // not very wide costs one small grid, not one workgroup per site
+  // persistent over the sites (one workgroup per CU fits)
   for (int64_t s = blockIdx.x; s < n_sites; s += gridDim.x) {
   __syncthreads();  // the previous site's scan is done with the LDS
   for (int i = tid; i < kBins / 8; i += kU16Threads)
@@ -1083,8 +952,7 @@ __global__ __launch_bounds__(kU16Threads) void k_hist_site_u16(
 void launch_hist_site_u16(const uint16_t* sites, int64_t npx, int64_t n_sites, uint32_t* slab,
                           const QPos& p, uint32_t* vlh, int64_t vlh_ld,
                           unsigned long long* pooled, unsigned long long* pooled_parts,
-                          int n_parts, int64_t* zero_counts, uint32_t* site_hist,
-                          const unsigned long long* wide, unsigned long long xthr, hipStream_t s,
+                          int64_t* zero_counts, uint32_t* site_hist, hipStream_t s,
                           const SiteTab& tab) {
   if (n_sites <= 0) return;
   ProfScope prof("hist_u16", s);
@@ -1095,9 +963,9 @@ void launch_hist_site_u16(const uint16_t* sites, int64_t npx, int64_t n_sites, u
   TMH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
   const unsigned grid = (unsigned)std::min<int64_t>(n_sites, cus);
   hipLaunchKernelGGL(k_hist_site_u16, dim3(grid), dim3(kU16Threads), 0, s, sites, npx, n_sites,
-                     slab, pp, vlh, pooled_parts, n_parts, zero_counts, site_hist, wide, xthr, tab);
+                     slab, pp, vlh, pooled_parts, kPooledParts, zero_counts, site_hist, tab);
   hipLaunchKernelGGL(k_pooled_fold, dim3(kBins / 256), dim3(256), 0, s, pooled, pooled_parts,
-                     n_parts, wide, xthr);
+                     kPooledParts);
   TMH_HIP(hipGetLastError());
 }
 

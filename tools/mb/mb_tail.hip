@@ -91,7 +91,7 @@ static int run(int argc, char** argv) {
   launch_synth(in, S, H, W, 12345, 0, 0, dist, 0);
   float4 *coef, *mconst2;
   uint32_t* hist;
-  unsigned long long *rmask, *fe, *pooled, *parts;
+  unsigned long long *rmask, *fe, *pooled;
   unsigned int* fn;
   uint32_t* sink;
   CK(hipMalloc(&coef, npx * 8));
@@ -102,8 +102,6 @@ static int run(int argc, char** argv) {
   CK(hipMalloc(&fn, 4));
   CK(hipMalloc(&sink, 64));
   CK(hipMalloc(&pooled, kBins * 8));
-  CK(hipMalloc(&parts, 16 * kBins * 8));
-  CK(hipMemset(parts, 0, 16 * kBins * 8));
   {
     std::vector<float> c(npx * 2);
     for (int64_t i = 0; i < npx * 2; ++i) c[i] = (i & 2) ? 1.02f : 8.3f;
@@ -183,17 +181,16 @@ static int run(int argc, char** argv) {
   time("load stream (order-stat bytes)", osb, [&] {
     hipLaunchKernelGGL(k_load, dim3(4096), dim3(256), 0, 0, (const uint4*)vlh, (int64_t)(os_bytes / 16), sink);
   });
-  auto fin = [&](auto kern, int nt) {
-    return [&, kern, nt] {
-      hipLaunchKernelGGL(kern, dim3((unsigned)S), dim3(nt), 0, 0, hist, rmask, 0, qp, vlh, parts, 16,
-                         zeros, (uint32_t*)nullptr, (const unsigned long long*)nullptr, 0ull);
+  TailJobs T{};
+  T.j[0] = TailJob{hist, rmask, nullptr, qp, vlh, pooled, zeros, nullptr, S};
+  T.n = 1;
+  auto fin = [&](auto kern) {
+    return [&, kern] {
+      hipLaunchKernelGGL(kern, dim3((unsigned)S), dim3(kHistThreads), 0, 0, T);
     };
   };
-  time("hfin 1024 (no reset)", osb, fin(k_hist_finalize<8, 1024>, 1024));
-  time("hfin 1024 no output", 0, fin(k_hist_finalize<9, 1024>, 1024));
-  time("hfin 1024 no pooled", osb, fin(k_hist_finalize<12, 1024>, 1024));
-  time("hfin 1024 scan only", 0, fin(k_hist_finalize<13, 1024>, 1024));
-  time("hfin 256 (no reset)", osb, fin(k_hist_finalize<8, 256>, 256));
+  time("hfin (no reset)", osb, fin(k_hist_finalize<8>));
+  time("hfin scan only (no reset, no output)", 0, fin(k_hist_finalize<9>));
   time("pct_acc prod", osb, [&] { launch_pct_accumulate(vlh, S, S, Q, gamma, acc, 0); });
   time("pct_acc U32", osb, [&] {
     hipLaunchKernelGGL(k_pct_acc_u<32>, dim3((unsigned)cdiv(Q, 256)), dim3(256), 0, 0, vlh, S,
