@@ -66,6 +66,19 @@ typedef struct tmh5_chunk {
 int tmh5_read_raw_chunks(const char* const* paths, int64_t n_files, int n_threads, uint8_t* blob,
                          int64_t blob_cap, tmh5_chunk* table, int64_t table_cap,
                          int64_t* blob_used, int64_t* n_chunks, int32_t* geom);
+/* The inverse: n_files channel images (height x width, bits 8 or 16) from
+ * chunks that are already zlib streams (libtmhip tmh_deflate_device, or any
+ * deflate coder).  Each file is created like tmh5_write_channel_image_chunked
+ * does (chunked, deflate filter recorded at level 4) and its chunks are stored
+ * as they are with H5Dwrite_chunk, filter mask 0 (flags 1: mask 1, raw bytes).
+ * table: n_chunks = n_files * grid entries, any order, each grid cell of
+ * each file (image = the file's index, (row0, col0) its origin) exactly once,
+ * src_off / src_len its stream in blob.  The files read back through H5Dread
+ * and through tmh5_read_raw_chunks.  n_threads workers, one file each. */
+int tmh5_write_channel_images_raw_chunks(const char* const* paths, int64_t n_files, int height,
+                                         int width, int bits, int chunk_rows, int chunk_cols,
+                                         const uint8_t* blob, const tmh5_chunk* table,
+                                         int64_t n_chunks, int n_threads);
 
 #ifdef __cplusplus
 }

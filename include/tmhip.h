@@ -703,6 +703,51 @@ int tmh_place_chunks_device(const uint8_t* dev_raw, const tmh_zchunk* dev_chunks
                             int height, int width, int elem_bytes, int chunk_rows, int chunk_cols,
                             void* dev_images, void* stream);
 
+/* ---- site-image output: GPU deflate of HDF5 gzip chunks -----------------
+ * The mirror of the input path, for imextract
+ * (tmlib/workflow/imextract/api.py:88-157: the planes of a site, their
+ * elementwise maximum when there are several, ChannelImageFile.put) and any
+ * caller with sites on the device.  tmh_gather_chunks_device cuts
+ * dev_images[n_images][height][width] (elem_bytes 1 or 2) into chunk-major
+ * raw bytes, edge chunks padded with zeros (HDF5's fill value), and fills
+ * raw_off, raw_len, image, row0, col0 of the n_images * ceil(height /
+ * chunk_rows) * ceil(width / chunk_cols) table entries (image-major, then
+ * row-major chunks).  tmh_deflate_device codes every chunk as one complete
+ * zlib stream (RFC 1950: CM 8, CINFO 7, dynamic-Huffman or stored blocks,
+ * Adler-32), packs the streams into dev_dst in table order and fills src_off
+ * and src_len: the table then feeds tmh_inflate_device and libtmh5's
+ * tmh5_write_channel_images_raw_chunks unchanged.  No stream is longer than
+ * tmh_deflate_bound(raw_len); dst_bytes must be at least n_chunks *
+ * tmh_deflate_bound(raw_max).  dev_status: TMH_Z_OK, or TMH_Z_INPUT for a
+ * table entry outside the raw buffer (src_len 0).  *dev_total_bytes (device
+ * memory): the bytes of all streams.  dev_scratch: at least
+ * tmh_deflate_scratch_bytes(n_chunks, raw_max) bytes, 16-byte aligned.  The
+ * bytes depend on the input alone (tests/deflate_host.cpp builds the same
+ * encoder for the CPU). */
+int64_t tmh_deflate_bound(int64_t raw_len);
+int64_t tmh_deflate_scratch_bytes(int64_t n_chunks, int64_t raw_max);
+int tmh_gather_chunks_device(const void* dev_images, int64_t n_images, int height, int width,
+                             int elem_bytes, int chunk_rows, int chunk_cols,
+                             tmh_zchunk* dev_chunks, uint8_t* dev_raw, void* stream);
+int tmh_deflate_device(const uint8_t* dev_raw, int64_t raw_bytes, tmh_zchunk* dev_chunks,
+                       int64_t n_chunks, int64_t raw_max, uint8_t* dev_dst, int64_t dst_bytes,
+                       void* dev_scratch, int64_t scratch_bytes, int32_t* dev_status,
+                       int64_t* dev_total_bytes, void* stream);
+/* dev_out[site] = the elementwise maximum of dev_planes[site][0..z), z >= 1
+ * (np.max(np.dstack(planes), axis=2)). */
+int tmh_zproject_max_device(const void* dev_planes, int64_t n_sites, int z, int height, int width,
+                            int elem_bytes, void* dev_out, void* stream);
+/* Host-buffer forms (unpipelined).  tmh_deflate_images: gather + deflate;
+ * host_chunks and host_status hold one entry per chunk, host_blob the packed
+ * streams (*total bytes; TMH_EINVAL with *total set when blob_capacity is
+ * smaller). */
+int tmh_deflate_images(const void* host_images, int64_t n_images, int height, int width,
+                       int elem_bytes, int chunk_rows, int chunk_cols, tmh_zchunk* host_chunks,
+                       uint8_t* host_blob, int64_t blob_capacity, int32_t* host_status,
+                       int64_t* total);
+int tmh_zproject_max(const void* host_planes, int64_t n_sites, int z, int height, int width,
+                     int elem_bytes, void* host_out);
+
 /* ---- device memory helpers for callers without another allocator -------- */
 int tmh_malloc_device(void** dev_ptr, size_t bytes);
 int tmh_free_device(void* dev_ptr);

@@ -436,6 +436,17 @@ void launch_inflate(const uint8_t* src, int64_t src_bytes, const tmh_zchunk* chu
 void launch_place_chunks(const uint8_t* raw, const tmh_zchunk* chunks, int64_t n_chunks,
                          int height, int width, int esize, int chunk_rows, int chunk_cols,
                          uint8_t* images, hipStream_t s);
+// site-image output (deflate_kernels.hip)
+int64_t deflate_bound_bytes(int64_t raw_len);
+int64_t deflate_scratch_bytes(int64_t n_chunks, int64_t raw_max);
+void launch_gather_chunks(const uint8_t* images, int64_t n_images, int height, int width,
+                          int esize, int chunk_rows, int chunk_cols, tmh_zchunk* chunks,
+                          uint8_t* raw, hipStream_t s);
+void launch_deflate(const uint8_t* raw, int64_t raw_bytes, tmh_zchunk* chunks, int64_t n_chunks,
+                    int64_t raw_max, uint8_t* dst, uint8_t* scratch, int32_t* status,
+                    int64_t* total, hipStream_t s);
+void launch_zproject_max(const void* planes, int64_t n_sites, int z, int height, int width,
+                         int esize, void* out, hipStream_t s);
 // illuminati tile pyramid (pyramid_kernels.hip); d_tbeg[n_tiles + 1]: tile t's
 // rectangles are d_rects[d_tbeg[t], d_tbeg[t + 1])
 void launch_tiles_base(const uint8_t* sites, int64_t n_sites, int H, int W,

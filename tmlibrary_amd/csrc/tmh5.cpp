@@ -640,6 +640,79 @@ int tmh5_read_raw_chunks(const char* const* paths, int64_t n_files, int n_thread
   });
 }
 
+// The writing mirror of tmh5_read_raw_chunks: every file gets the dataset
+// tmh5_write_channel_image_chunked creates (chunked, deflate recorded at
+// level 4), its chunks stored as given with H5Dwrite_chunk (filter mask 0:
+// "the deflate filter was applied"), no filter run by libhdf5.
+int tmh5_write_channel_images_raw_chunks(const char* const* paths, int64_t n_files, int height,
+                                         int width, int bits, int chunk_rows, int chunk_cols,
+                                         const uint8_t* blob, const tmh5_chunk* table,
+                                         int64_t n_chunks, int n_threads) {
+  return guard([&] {
+    silence();
+    if (n_files < 0 || n_chunks < 0 || (n_files > 0 && (!paths || !blob || !table)) ||
+        height <= 0 || width <= 0 || (bits != 8 && bits != 16) || chunk_rows <= 0 ||
+        chunk_cols <= 0 || chunk_rows > height || chunk_cols > width)
+      throw H5Err{-22, "bad arguments"};
+    if (n_files == 0) return;
+    const int64_t gr = (height + chunk_rows - 1) / chunk_rows, gc = (width + chunk_cols - 1) / chunk_cols;
+    if (n_chunks != n_files * gr * gc) throw H5Err{-22, "the table must hold every chunk of every file"};
+    // table entries by file and grid cell, each exactly once
+    std::vector<int64_t> cell((size_t)n_chunks, -1);
+    for (int64_t k = 0; k < n_chunks; ++k) {
+      const tmh5_chunk& e = table[k];
+      if (e.image < 0 || e.image >= n_files || e.row0 < 0 || e.col0 < 0 || e.row0 % chunk_rows ||
+          e.col0 % chunk_cols || e.row0 >= height || e.col0 >= width || e.src_off < 0 ||
+          e.src_len <= 0 || e.src_len > 0xFFFFFFFFll || (e.flags & ~1))
+        throw H5Err{-22, "bad chunk table entry"};
+      int64_t& c = cell[(size_t)((e.image * gr + e.row0 / chunk_rows) * gc + e.col0 / chunk_cols)];
+      if (c >= 0) throw H5Err{-22, "a chunk appears twice in the table"};
+      c = k;
+    }
+    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads > 0 ? n_threads : 1, n_files));
+    std::atomic<int64_t> next{0};
+    std::atomic<bool> failed{false};
+    std::string first_err;
+    std::mutex m;
+    auto work = [&] {
+      for (;;) {
+        const int64_t i = next.fetch_add(1);
+        if (i >= n_files || failed.load()) return;
+        try {
+          if (!paths[i]) throw H5Err{-22, "path is NULL"};
+          Hid f(H5Fcreate(paths[i], H5F_ACC_TRUNC, H5P_DEFAULT, H5P_DEFAULT), H5Fclose);
+          const hsize_t d2[2] = {(hsize_t)height, (hsize_t)width};
+          const hsize_t chunk[2] = {(hsize_t)chunk_rows, (hsize_t)chunk_cols};
+          Hid dcpl(H5Pcreate(H5P_DATASET_CREATE), H5Pclose);
+          H5Pset_chunk(dcpl, 2, chunk);
+          H5Pset_deflate(dcpl, 4);
+          Hid lcpl(H5Pcreate(H5P_LINK_CREATE), H5Pclose);
+          H5Pset_create_intermediate_group(lcpl, 1);
+          Hid sp(H5Screate_simple(2, d2, nullptr), H5Sclose);
+          Hid ds(H5Dcreate2(f, "array", bits == 8 ? H5T_STD_U8LE : H5T_STD_U16LE, sp, lcpl, dcpl,
+                            H5P_DEFAULT),
+                 H5Dclose);
+          for (int64_t g = 0; g < gr * gc; ++g) {
+            const tmh5_chunk& e = table[cell[(size_t)(i * gr * gc + g)]];
+            const hsize_t coord[2] = {(hsize_t)e.row0, (hsize_t)e.col0};
+            if (H5Dwrite_chunk(ds, H5P_DEFAULT, (uint32_t)(e.flags & 1), coord, (size_t)e.src_len,
+                               blob + e.src_off) < 0)
+              throw H5Err{-5, std::string(paths[i]) + ": writing a chunk failed"};
+          }
+        } catch (const H5Err& e) {
+          std::lock_guard<std::mutex> lk(m);
+          if (!failed.exchange(true)) first_err = e.msg;
+        }
+      }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+    if (failed) throw H5Err{-5, first_err};
+  });
+}
+
 int tmh5_read_channel_images(const char* const* paths, int64_t n_files, void* out, int n_threads) {
   return guard([&] {
     silence();

@@ -123,6 +123,14 @@ SIGNATURES = {
     "tmh_inflate_scratch_bytes": (_I64, [_I64, _I64]),
     "tmh_inflate_device": (_I, [_P, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P]),
     "tmh_place_chunks_device": (_I, [_P, _P, _I64, _I, _I, _I, _I, _I, _P, _P]),
+    "tmh_deflate_bound": (_I64, [_I64]),
+    "tmh_deflate_scratch_bytes": (_I64, [_I64, _I64]),
+    "tmh_gather_chunks_device": (_I, [_P, _I64, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "tmh_deflate_device": (_I, [_P, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
+    "tmh_zproject_max_device": (_I, [_P, _I64, _I, _I, _I, _I, _P, _P]),
+    "tmh_deflate_images": (_I, [_P, _I64, _I, _I, _I, _I, _I, _P, _P, _I64, _P,
+                                C.POINTER(_I64)]),
+    "tmh_zproject_max": (_I, [_P, _I64, _I, _I, _I, _I, _P]),
     "tmh_malloc_device": (_I, [C.POINTER(_P), C.c_size_t]),
     "tmh_free_device": (_I, [_P]),
     "tmh_memcpy": (_I, [_P, _P, C.c_size_t, _I, _P]),

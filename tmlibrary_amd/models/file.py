@@ -49,6 +49,10 @@ _SIGS = {
     "tmh5_read_raw_chunks": (C.c_int, [C.POINTER(C.c_char_p), C.c_int64, C.c_int, C.c_void_p,
                                        C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int64), C.c_void_p]),
+    "tmh5_write_channel_images_raw_chunks": (C.c_int, [C.POINTER(C.c_char_p), C.c_int64, C.c_int,
+                                                       C.c_int, C.c_int, C.c_int, C.c_int,
+                                                       C.c_void_p, C.c_void_p, C.c_int64,
+                                                       C.c_int]),
 }
 
 #: struct tmh5_chunk (include/tmh5.h) = struct tmh_zchunk (include/tmhip.h)
@@ -158,6 +162,65 @@ def write_channel_image(path, array, gzip_level=4, chunks=None):
     cr, cc = (0, 0) if chunks == "rows" else (int(chunks[0]), int(chunks[1]))
     _check(L.tmh5_write_channel_image_chunked(_b(path), a.shape[0], a.shape[1], 8 * a.itemsize,
                                               a.ctypes.data, int(gzip_level), cr, cc), path)
+
+
+def write_raw_chunks(paths, height, width, bits, chunk_rows, chunk_cols, blob, table,
+                     n_threads=None):
+    """Channel image files from chunks that are already zlib streams (libtmh5
+    tmh5_write_channel_images_raw_chunks; the inverse of ``read_raw_chunks``):
+    ``table`` a CHUNK_DTYPE array with every chunk of every file (image = the
+    index into ``paths``), ``blob`` the streams."""
+    paths = list(paths)
+    L = h5lib()
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    table = np.ascontiguousarray(table)
+    if table.dtype.itemsize != CHUNK_DTYPE.itemsize:
+        raise ValueError("table must be a CHUNK_DTYPE array")
+    if len(table) and int((table["src_off"] + table["src_len"]).max()) > blob.nbytes:
+        raise ValueError("a chunk lies outside the blob")
+    arr = (C.c_char_p * len(paths))(*[_b(p) for p in paths])
+    nt = default_decode_threads() if n_threads is None else int(n_threads)
+    _check(L.tmh5_write_channel_images_raw_chunks(arr, len(paths), int(height), int(width),
+                                                  int(bits), int(chunk_rows), int(chunk_cols),
+                                                  blob.ctypes.data, table.ctypes.data, len(table),
+                                                  nt), paths[0] if paths else "")
+
+
+def write_channel_images(paths, arrays, encode="auto", chunks=None):
+    """Many channel image files at once: ``arrays`` [n, H, W] uint8/uint16 (a
+    numpy array, a sequence of 2-D arrays of one shape, or a device tensor),
+    ``arrays[i]`` into ``paths[i]`` with the layout of ``write_channel_image``
+    (gzip level 4 recorded).  ``encode``: "gpu": the chunks are deflated on the
+    GPU (models/device_encode.py) and stored as they are; "host": libhdf5's
+    deflate filter, file by file; "auto": "gpu" when a device is present (or
+    ``arrays`` is a device tensor), else "host"."""
+    if encode not in ("auto", "gpu", "host"):
+        raise ValueError('encode must be "auto", "gpu" or "host"')
+    paths = list(paths)
+    on_device = hasattr(arrays, "is_cuda") and arrays.is_cuda
+    if encode == "auto":
+        encode = "gpu"
+        if not on_device:
+            from tmlibrary_amd import hip
+            try:
+                hip.lib()
+            except hip.HipUnavailableError:
+                encode = "host"
+    if encode == "gpu":
+        from tmlibrary_amd.models.device_encode import write_channel_images_device
+        if not (on_device or isinstance(arrays, np.ndarray)):
+            arrays = np.stack([np.asarray(a) for a in arrays]) if len(arrays) else \
+                np.empty((0, 1, 1), np.uint16)
+        write_channel_images_device(paths, arrays, chunks)
+        return
+    if on_device:
+        arrays = arrays.cpu().numpy()
+        if arrays.dtype == np.int16:
+            arrays = arrays.view(np.uint16)
+    if len(arrays) != len(paths):
+        raise ValueError("%d paths for %d sites" % (len(paths), len(arrays)))
+    for p, a in zip(paths, arrays):
+        write_channel_image(p, a, gzip_level=4, chunks=chunks)
 
 
 def read_channel_image(path):
