@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TMH_ABI_VERSION 7
+#define TMH_ABI_VERSION 8
 
 #define TMH_OK 0
 #define TMH_EINVAL (-22)  /* bad argument: maps to ValueError / TypeError */
@@ -747,6 +747,72 @@ int tmh_deflate_images(const void* host_images, int64_t n_images, int height, in
                        int64_t* total);
 int tmh_zproject_max(const void* host_planes, int64_t n_sites, int z, int height, int width,
                      int elem_bytes, void* host_out);
+
+/* ---- jterator: a site's channel stacks and object tables -------------------
+ * What jterator computes around its modules (which live in another package).
+ *
+ * Input, tmlib/workflow/jterator/api.py:283-316 (_load_pipeline_input): every
+ * plane (z-plane x time point) of a channel is corrected, aligned with
+ * crop=True and written to image_array[:, :, zplane, tpoint] of a
+ * (aligned_height, aligned_width, n_zplanes, n_tpoints) array.  One launch
+ * for all planes of a channel: planes [n_planes][height][width] uint16, the
+ * output [n_sites][out_h][out_w][slots] with slot = zplane * n_tpoints +
+ * tpoint, i.e. n_sites C-ordered [out_h][out_w][n_zplanes][n_tpoints] arrays.
+ * Element (site, r, c, slot) is the corrected pixel (src_r0 + r, src_c0 + c) of
+ * the plane with host_site[p] == site and host_slot[p] == slot -- the value
+ * tmh_correct_u16_device writes for it without a clip, bit for bit -- or the
+ * raw pixel when c is NULL (a channel that is not corrected); a (site, slot)
+ * no plane maps to is 0 (np.zeros), written by the same launch.  host_windows
+ * [n_planes] are the planes' crop=True windows; only src_r0, src_c0, rows and
+ * cols are read.  TMH_EINVAL, nothing launched: two planes on one (site,
+ * slot); a window whose rows / cols differ from (out_h, out_w) (the
+ * reference's numpy assignment raises there) or which leaves the source; a
+ * site or slot index out of range; a corrector of another image size; more
+ * than 65,535 sites.  dev_out must not overlap dev_in; both are 2-byte
+ * aligned (the 16-byte forms of slots == 1 want dev_in, corrected, or
+ * dev_out, not corrected, 16-byte aligned).  Queued on `stream` (NULL: the
+ * corrector's, or the default stream without one); the call returns when the
+ * stack is complete. */
+int tmh_correct_stack_u16_device(tmh_corrector* c, const uint16_t* dev_in, uint16_t* dev_out,
+                                 int64_t n_planes, int height, int width,
+                                 const int32_t* host_site, const int32_t* host_slot,
+                                 const tmh_window* host_windows, int64_t n_sites, int slots,
+                                 int out_h, int out_w, void* stream);
+int tmh_correct_stack_u16(tmh_corrector* c, const uint16_t* host_in, uint16_t* host_out,
+                          int64_t n_planes, int height, int width, const int32_t* host_site,
+                          const int32_t* host_slot, const tmh_window* host_windows,
+                          int64_t n_sites, int slots, int out_h, int out_w);
+
+/* Output, tmlib/workflow/jterator/handles.py:399-551 and tmlib/image.py:796:
+ * the integer sums behind SegmentedObjects' labels, mh.labeled.bbox, centroids
+ * (mh.center_of_mass(plane, labels=plane)) and is_border, one row per label
+ * 0..max_label of one int32 label plane [height][width] (label 0, the
+ * background, gets a row like any other; mahotas does the same).  Every field
+ * is exact and independent of scheduling. */
+typedef struct tmh_object_row {
+  int64_t n, sum_y, sum_x;  /* pixel count, sum of row indices, sum of column indices */
+  int32_t y0, y1, x0, x1;   /* mh.labeled.bbox: [min_y, max_y+1, min_x, max_x+1]; n == 0: all 0 */
+  int32_t border, pad;      /* 1 if the label occurs in row 0, row H-1, column 0 or column W-1 */
+} tmh_object_row;
+/* dev_max[p] / dev_min[p] = the largest / smallest label of plane p, on
+ * `stream` (NULL: the default stream), asynchronously. */
+int tmh_label_max_device(const int32_t* dev_planes, int64_t n_planes, int height, int width,
+                         int32_t* dev_max, int32_t* dev_min, void* stream);
+/* dev_rows [n_planes][max_label + 1].  A negative label or a label above
+ * max_label in any plane: TMH_EINVAL with dev_rows untouched -- found from
+ * tmh_label_max_device's result, which the call computes and waits for first,
+ * never by an out-of-range write.  The table is then queued on `stream`
+ * (NULL: the default stream).  At most 65,535 planes per call; n_planes = 0
+ * does nothing. */
+int tmh_object_table_device(const int32_t* dev_planes, int64_t n_planes, int height, int width,
+                            int32_t max_label, tmh_object_row* dev_rows, void* stream);
+/* Host buffers.  *max_label = the largest label of all planes (at least 0);
+ * host_rows [n_planes][*max_label + 1], caller-owned like every host pointer
+ * here, with room for row_capacity rows: a smaller capacity (or host_rows
+ * NULL) is TMH_EINVAL with *max_label set and nothing written, so a caller
+ * sizes the table from a first call.  A negative label: TMH_EINVAL. */
+int tmh_object_table(const int32_t* host_planes, int64_t n_planes, int height, int width,
+                     int32_t* max_label, tmh_object_row* host_rows, int64_t row_capacity);
 
 /* ---- device memory helpers for callers without another allocator -------- */
 int tmh_malloc_device(void** dev_ptr, size_t bytes);

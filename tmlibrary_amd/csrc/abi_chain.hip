@@ -48,9 +48,106 @@ static void correct_chain_u8_dev(tmh_corrector* c, const uint16_t* dev_in, uint8
   TMH_HIP(hipStreamSynchronize(s));  // the window buffer is reused by the next call
 }
 
+// argument checks of the jterator channel stack, and its device table
+// (launch_stack_u16): plane of each (site, slot), site and slot of each plane,
+// the planes' windows
+static std::vector<int32_t> stack_table(tmh_corrector* c, const void* in, const void* out,
+                                        int64_t n_planes, int H, int W, const int32_t* site,
+                                        const int32_t* slot, const tmh_window* win,
+                                        int64_t n_sites, int slots, int out_h, int out_w) {
+  TMH_CHECK(n_planes >= 0 && n_sites >= 0 && slots >= 1 && H > 0 && W > 0 && out_h >= 0 &&
+                out_w >= 0,
+            TMH_EINVAL, "bad arguments");
+  TMH_CHECK(n_planes == 0 || (in && site && slot && win), TMH_EINVAL, "bad arguments");
+  TMH_CHECK(out || n_sites == 0 || out_h == 0 || out_w == 0, TMH_EINVAL, "bad arguments");
+  TMH_CHECK(n_sites <= 65535, TMH_EINVAL, "at most 65,535 sites per stack call");
+  TMH_CHECK(n_sites * slots < ((int64_t)1 << 31), TMH_EINVAL, "too many (site, slot) pairs");
+  TMH_CHECK((int64_t)out_h * out_w <= (int64_t)65535 * 2048, TMH_EINVAL,
+            "at most 65,535 x 2,048 pixels per aligned site");
+  TMH_CHECK(!c || (c->H == H && c->W == W), TMH_EINVAL,
+            "the corrector was made for another image size");
+  std::vector<int32_t> t((size_t)(n_sites * slots + 8 * n_planes), -1);
+  int32_t* site_of = t.data() + n_sites * slots;
+  int32_t* slot_of = site_of + n_planes;
+  tmh_window* w = reinterpret_cast<tmh_window*>(slot_of + n_planes);
+  for (int64_t p = 0; p < n_planes; ++p) {
+    TMH_CHECK(site[p] >= 0 && site[p] < n_sites, TMH_EINVAL, "site index out of range");
+    TMH_CHECK(slot[p] >= 0 && slot[p] < slots, TMH_EINVAL, "slot index out of range");
+    int32_t& owner = t[(size_t)site[p] * slots + slot[p]];
+    TMH_CHECK(owner < 0, TMH_EINVAL, "two planes map to one (site, slot)");
+    owner = (int32_t)p;
+    TMH_CHECK(win[p].rows == out_h && win[p].cols == out_w, TMH_EINVAL,
+              "could not broadcast a window's extent into the stack's (out_h, out_w)");
+    TMH_CHECK(win[p].src_r0 >= 0 && win[p].src_c0 >= 0 &&
+                  (int64_t)win[p].src_r0 + out_h <= H && (int64_t)win[p].src_c0 + out_w <= W,
+              TMH_EINVAL, "alignment window leaves the source image");
+    site_of[p] = site[p];
+    slot_of[p] = slot[p];
+    w[p] = win[p];
+  }
+  return t;
+}
+
+static void correct_stack_u16_dev(tmh_corrector* c, const uint16_t* dev_in, uint16_t* dev_out,
+                                  int64_t n_planes, int H, int W, const int32_t* host_site,
+                                  const int32_t* host_slot, const tmh_window* host_windows,
+                                  int64_t n_sites, int slots, int out_h, int out_w, void* stream) {
+  const std::vector<int32_t> t = stack_table(c, dev_in, dev_out, n_planes, H, W, host_site,
+                                             host_slot, host_windows, n_sites, slots, out_h, out_w);
+  if (n_sites == 0 || out_h == 0 || out_w == 0) return;
+  hipStream_t s = pick(c ? c->stream : nullptr, stream);
+  const int any_unmapped =
+      std::count(t.begin(), t.begin() + n_sites * slots, (int32_t)-1) > 0 ? 1 : 0;
+  DBuf<int32_t> tab;
+  tab.alloc(t.size());
+  TMH_HIP(hipMemcpyAsync(tab.p, t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  if (c) {
+    const FixList fl = corrector_fixlist(c, n_planes, s);
+    corrector_forms(c, s);
+    launch_stack_u16(dev_in, dev_out, n_planes, H, W, n_sites, slots, out_h, out_w, tab.p,
+                     c->coef.p, c->lut.p, c->mconst.p, fl, c->coef64.p, c->rc.p, c->log_transform,
+                     any_unmapped, s);
+  } else {
+    launch_stack_u16(dev_in, dev_out, n_planes, H, W, n_sites, slots, out_h, out_w, tab.p, nullptr,
+                     nullptr, nullptr, FixList{nullptr, nullptr, 0u}, nullptr, nullptr, 0,
+                     any_unmapped, s);
+  }
+  TMH_HIP(hipStreamSynchronize(s));  // the table is freed on return
+}
+
 }  // namespace tmh
 
 extern "C" {
+
+int tmh_correct_stack_u16_device(tmh_corrector* c, const uint16_t* dev_in, uint16_t* dev_out,
+                                 int64_t n_planes, int height, int width,
+                                 const int32_t* host_site, const int32_t* host_slot,
+                                 const tmh_window* host_windows, int64_t n_sites, int slots,
+                                 int out_h, int out_w, void* stream) {
+  return guard([&] {
+    correct_stack_u16_dev(c, dev_in, dev_out, n_planes, height, width, host_site, host_slot,
+                          host_windows, n_sites, slots, out_h, out_w, stream);
+  });
+}
+
+int tmh_correct_stack_u16(tmh_corrector* c, const uint16_t* host_in, uint16_t* host_out,
+                          int64_t n_planes, int height, int width, const int32_t* host_site,
+                          const int32_t* host_slot, const tmh_window* host_windows,
+                          int64_t n_sites, int slots, int out_h, int out_w) {
+  return guard([&] {
+    // (checked before anything is uploaded; the shared body checks again)
+    stack_table(c, host_in, host_out, n_planes, height, width, host_site, host_slot, host_windows,
+                n_sites, slots, out_h, out_w);
+    const size_t out_n = (size_t)n_sites * out_h * out_w * slots;
+    if (out_n == 0) return;
+    DBuf<uint16_t> a, b;
+    if (n_planes > 0) a.upload(host_in, (size_t)n_planes * height * width);
+    b.alloc(out_n);
+    correct_stack_u16_dev(c, a.p, b.p, n_planes, height, width, host_site, host_slot, host_windows,
+                          n_sites, slots, out_h, out_w, nullptr);
+    b.download(host_out, out_n);
+  });
+}
 
 int tmh_align(const void* host_in, void* host_out, int elem_bytes, int64_t n_sites, int height,
               int width, const tmh_window* windows, int out_height, int out_width) {

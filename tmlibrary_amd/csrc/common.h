@@ -428,6 +428,20 @@ void launch_chain_u8(const uint16_t* in, uint8_t* out, int H, int W, int64_t n_s
                      const double2* coef64, const RefineConst* rc, int log_transform,
                      const tmh_window* d_win, int lo, int hi, uint8_t* lut8, hipStream_t s,
                      double zero_log10 = -10.0);
+// jterator channel stack (chain_kernels.hip): d_tab = int32 [n_sites * slots]
+// plane of each (site, slot) or -1, [n_planes] site, [n_planes] slot,
+// [n_planes] windows; coef == null: raw pixels; any_unmapped: some (site, slot)
+// has no plane.  Launches its own fixup.
+void launch_stack_u16(const uint16_t* in, uint16_t* out, int64_t n_planes, int H, int W,
+                      int64_t n_sites, int slots, int out_h, int out_w, const int32_t* d_tab,
+                      const float4* coef, const float2* lut, const float4* mconst, const FixList& fl,
+                      const double2* coef64, const RefineConst* rc, int log_transform,
+                      int any_unmapped, hipStream_t s);
+// jterator object tables (objects_kernels.hip)
+void launch_label_minmax(const int32_t* planes, int64_t n_planes, int64_t npx, int32_t* d_max,
+                         int32_t* d_min, hipStream_t s);
+void launch_object_table(const int32_t* planes, int64_t n_planes, int H, int W, int32_t max_label,
+                         tmh_object_row* rows, hipStream_t s);
 // site-image input (inflate_kernels.hip)
 int64_t inflate_scratch_bytes(int64_t n_chunks, int64_t raw_max);
 void launch_inflate(const uint8_t* src, int64_t src_bytes, const tmh_zchunk* chunks,

@@ -33,7 +33,7 @@ TMH_FUSED_NO_HIST = 100
 TMH_SYNTH_STANDARD = 0
 TMH_SYNTH_BRIGHT = 1
 TMH_SYNTH_UNIFORM = 2
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _P = C.c_void_p
 _I64 = C.c_int64
@@ -131,6 +131,12 @@ SIGNATURES = {
     "tmh_deflate_images": (_I, [_P, _I64, _I, _I, _I, _I, _I, _P, _P, _I64, _P,
                                 C.POINTER(_I64)]),
     "tmh_zproject_max": (_I, [_P, _I64, _I, _I, _I, _I, _P]),
+    "tmh_correct_stack_u16_device": (_I, [_P, _P, _P, _I64, _I, _I, _P, _P, _P, _I64, _I, _I, _I,
+                                          _P]),
+    "tmh_correct_stack_u16": (_I, [_P, _P, _P, _I64, _I, _I, _P, _P, _P, _I64, _I, _I, _I]),
+    "tmh_label_max_device": (_I, [_P, _I64, _I, _I, _P, _P, _P]),
+    "tmh_object_table_device": (_I, [_P, _I64, _I, _I, C.c_int32, _P, _P]),
+    "tmh_object_table": (_I, [_P, _I64, _I, _I, C.POINTER(C.c_int32), _P, _I64]),
     "tmh_malloc_device": (_I, [C.POINTER(_P), C.c_size_t]),
     "tmh_free_device": (_I, [_P]),
     "tmh_memcpy": (_I, [_P, _P, C.c_size_t, _I, _P]),
@@ -149,6 +155,13 @@ WINDOW_DTYPE = np.dtype([("src_r0", np.int32), ("src_c0", np.int32), ("dst_r0", 
 TILE_RECT_DTYPE = np.dtype([(k, np.int32) for k in ("tile", "site", "src_y", "src_x", "dst_y",
                                                     "dst_x", "height", "width")])
 assert TILE_RECT_DTYPE.itemsize == 32
+
+
+#: struct tmh_object_row (include/tmhip.h): one label of one plane's object table
+OBJECT_ROW_DTYPE = np.dtype([("n", np.int64), ("sum_y", np.int64), ("sum_x", np.int64),
+                             ("y0", np.int32), ("y1", np.int32), ("x0", np.int32),
+                             ("x1", np.int32), ("border", np.int32), ("pad", np.int32)])
+assert OBJECT_ROW_DTYPE.itemsize == 48
 
 
 #: struct tmh_zchunk (include/tmhip.h): one HDF5 gzip chunk of the input path

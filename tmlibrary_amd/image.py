@@ -631,6 +631,100 @@ class PyramidTile(Image):
         return out
 
 
+def correct_stack(corrector, planes: np.ndarray, site, slot, windows, n_sites: int, slots: int,
+                  out_shape) -> np.ndarray:
+    """jterator's input loop (jterator/api.py:283-316) for the uint16 planes
+    [n, H, W] of one channel in one launch: plane p corrected (``corrector``
+    None: not corrected), cropped to its crop=True window and written to slot
+    ``slot[p]`` of site ``site[p]``.  Returns [n_sites, out_h, out_w, slots];
+    a (site, slot) no plane maps to is 0."""
+    a = np.ascontiguousarray(planes)
+    if a.dtype != np.uint16 or a.ndim != 3:
+        raise TypeError("the stack takes uint16 planes [n, H, W]")
+    if corrector is not None and a.shape[-2:] != corrector.shape:
+        raise ValueError("operands could not be broadcast together with shapes %s %s"
+                         % (a.shape, corrector.shape))
+    site = np.ascontiguousarray(site, dtype=np.int32).reshape(-1)
+    slot = np.ascontiguousarray(slot, dtype=np.int32).reshape(-1)
+    win = np.ascontiguousarray(np.asarray(windows, dtype=hip.WINDOW_DTYPE).reshape(-1))
+    if not (site.size == slot.size == win.size == a.shape[0]):
+        raise ValueError("one site, slot and alignment window per plane is required")
+    oh, ow = int(out_shape[0]), int(out_shape[1])
+    out = np.empty((int(n_sites), oh, ow, int(slots)), dtype=np.uint16)
+    hip.check(hip.lib().tmh_correct_stack_u16(
+        None if corrector is None else corrector._h, hip.ptr(a), hip.ptr(out), a.shape[0],
+        a.shape[1], a.shape[2], hip.ptr(site), hip.ptr(slot), hip.ptr(win), int(n_sites),
+        int(slots), oh, ow))
+    return out
+
+
+def object_tables(planes: np.ndarray) -> np.ndarray:
+    """The object tables of int32 label planes [n, H, W] in one call: a
+    structured array [n, max_label + 1] of ``hip.OBJECT_ROW_DTYPE`` (pixel
+    count, row and column sums, mh.labeled.bbox, border flag per label;
+    max_label over all planes).  A negative label raises ValueError."""
+    a = np.ascontiguousarray(planes)
+    if a.dtype != np.int32 or a.ndim != 3:
+        raise TypeError("label planes must be an int32 array [n, H, W]")
+    L = hip.lib()
+    n = a.shape[0]
+    if n == 0 or a.shape[1] == 0 or a.shape[2] == 0:
+        return np.zeros((n, 1), dtype=hip.OBJECT_ROW_DTYPE)
+    mx = C.c_int32(0)
+    per = 4096  # rows per plane of the first attempt; a larger table is sized from *max_label
+    while True:
+        rows = np.empty((n, per), dtype=hip.OBJECT_ROW_DTYPE)
+        rc = L.tmh_object_table(hip.ptr(a), n, a.shape[1], a.shape[2], C.byref(mx), hip.ptr(rows),
+                                rows.size)
+        if rc == hip.TMH_EINVAL and mx.value + 1 > per:
+            per = mx.value + 1
+            continue
+        hip.check(rc)
+        return rows.reshape(-1)[:n * (mx.value + 1)].reshape(n, mx.value + 1)
+
+
+class SegmentationImage(Image):
+    """A labeled image, one positive int32 identifier per segmented object
+    (tmlib/image.py:696-738).  The per-object numbers ``extract_polygons``
+    starts from come from the GPU's object table; the contour half of
+    ``extract_polygons`` and ``create_from_polygons`` are not built."""
+
+    __slots__ = ()
+
+    def __init__(self, array, metadata=None):
+        super(SegmentationImage, self).__init__(array, metadata)
+        if not self.is_int32:
+            raise TypeError("Image must have 32-bit integer type.")
+
+    @property
+    def is_int32(self):
+        return self.array.dtype == np.int32
+
+    @property
+    def array(self):
+        return self._array
+
+    @array.setter
+    def array(self, value):
+        if not isinstance(value, np.ndarray):
+            raise TypeError('Argument "array" must have type numpy.ndarray.')
+        if value.ndim != 2:
+            raise ValueError('Argument "array" must be two dimensional.')
+        if not value.dtype == np.int32:
+            raise ValueError('Argument "array" must have numpy.int32 data type.')
+        self._array = value
+
+    def object_table(self):
+        """One ``hip.OBJECT_ROW_DTYPE`` row per label 0..max of the plane."""
+        return object_tables(self.array[None])[0]
+
+    def bboxes(self):
+        """mh.labeled.bbox(self.array) (image.py:796): [max_label + 1, 4] rows
+        [min_y, max_y + 1, min_x, max_x + 1], zeros for absent labels."""
+        t = self.object_table()
+        return np.stack([t["y0"], t["y1"], t["x0"], t["x1"]], axis=1).astype(np.intp)
+
+
 class IllumstatsImage(Image):
     """float64 statistics plane (tmlib/image.py:1097-1136)."""
 
