@@ -300,6 +300,86 @@ def test_chain_without_log_transform(L, bounds):
         assert (d == 0).mean() > 0.99
 
 
+# shift classes of the 40 x 512 launch-regime test: destination offset
+# y * 512 + x -- none, +-512 (line-aligned; the last workgroup pads the
+# negative one), +-8 (8-byte but not line-aligned), two odd offsets, and an
+# empty window (rows = 0: all padding)
+_REGIME_SHIFTS = [(0, 0), (1, 0), (-1, 0), (0, 8), (0, -8), (3, -5), (-4, 7), None]
+_REGIME_RES = (4, 4, 16, 16)
+
+
+@pytest.fixture(scope="module")
+def regime_inputs():
+    from tmlibrary_amd.image import align_window
+    from tmlibrary_amd.synth import synth_sites_host
+    H, W, n = 40, 512, 130
+    st = orc.run_illumstats(synth_sites_host(5, H, W, seed=141))
+    sm, ss = orc.smooth_reflect(st.mean), orc.smooth_reflect(st.std)
+    sites = np.stack(synth_sites_host(n, H, W, seed=142))
+    wins = []
+    for i in range(n):
+        sh = _REGIME_SHIFTS[i % len(_REGIME_SHIFTS)]
+        w = align_window((H, W), *(sh or (2, 3)), *_REGIME_RES, crop=False)[0]
+        if sh is None:
+            w["rows"] = 0
+        wins.append(w)
+    return sm, ss, sites, np.stack(wins)
+
+
+@pytest.mark.parametrize("n_sites", [70, 130])
+def test_chain_launch_regimes(L, regime_inputs, n_sites):
+    """Sites of 40 x 512 (2,560 eight-pixel groups: two full 1,024-thread
+    workgroups and a partial third) in launches of 70 sites (8 site parts) and
+    130 (16 parts, a ragged last one), the shift classes of _REGIME_SHIFTS in
+    turn.  A site's bytes must not depend on how a launch is partitioned: the
+    one-call output equals, byte for byte, the same sites and windows run 7
+    per call (one part each); and the first site of every shift class is
+    within 1 of the oracle chain."""
+    import ctypes as C
+    from tmlibrary_amd import hip
+    from tmlibrary_amd.image import Corrector
+    sm, ss, sites, wins = regime_inputs
+    sites, wins = sites[:n_sites], np.ascontiguousarray(wins[:n_sites])
+    H, W = sites.shape[1:]
+    lo, hi = 100, 3000
+    corr = Corrector(sm, ss)
+    d_in, d_out = C.c_void_p(), C.c_void_p()
+    assert L.tmh_malloc_device(C.byref(d_in), sites.nbytes) == 0
+    assert L.tmh_malloc_device(C.byref(d_out), sites.size) == 0
+    assert L.tmh_memcpy(d_in, sites.ctypes.data, sites.nbytes, 0, None) == 0
+
+    def run(s0, n):
+        w = np.ascontiguousarray(wins[s0:s0 + n])
+        hip.check(L.tmh_correct_chain_u8_device(
+            corr._h, C.c_void_p(d_in.value + s0 * H * W * 2), C.c_void_p(d_out.value + s0 * H * W),
+            n, hip.ptr(w), lo, hi, None))
+
+    def fetch():
+        out = np.empty(sites.shape, np.uint8)
+        assert L.tmh_memcpy(out.ctypes.data, d_out, out.nbytes, 1, None) == 0
+        return out
+
+    junk = np.full(sites.shape, 0xA5, np.uint8)  # each run must write every byte itself
+    assert L.tmh_memcpy(d_out, junk.ctypes.data, junk.nbytes, 0, None) == 0
+    run(0, n_sites)
+    whole = fetch()
+    assert L.tmh_memcpy(d_out, junk.ctypes.data, junk.nbytes, 0, None) == 0
+    for s0 in range(0, n_sites, 7):
+        run(s0, min(7, n_sites - s0))
+    pieces = fetch()
+    L.tmh_free_device(d_in)
+    L.tmh_free_device(d_out)
+    corr.close()
+    assert np.array_equal(whole, pieces)
+    for i, sh in enumerate(_REGIME_SHIFTS):
+        if sh is None:
+            assert not whole[i].any()
+            continue
+        want = orc.illuminati_chain(sites[i], sm, ss, sh, _REGIME_RES, lo, hi)
+        d = np.abs(whole[i].astype(np.int32) - want.astype(np.int32))
+        assert d.max() <= 1, (i, sh, int(d.max()))
+
+
 def test_chain_rejects_bad_windows(L):
     from tmlibrary_amd.image import Corrector, align_window
     g, wins = _chain_inputs()

@@ -176,7 +176,7 @@ static void stats_welford_dev(tmh_stats* h, const uint16_t* dev_sites, int64_t n
     stats_probe(h, dev_sites, n_sites, tab, s);
   launch_welford(dev_sites, h->npx, n_sites, h->n, h->rn.p, h->mean.p, h->m2.p, h->lut_log.p,
                  log_transform, h->wf_part.p, h->wf_part.n, h->wf_parts, h->wide.p,
-                 probe_bright(h) ? 1 : 0, s, -1, tab);
+                 probe_bright(h) ? 1 : 0, s, tab);
   if ((h->npx & 7) == 0) h->wide_sites += n_sites;
   h->n += n_sites;
   h->pending += n_sites;

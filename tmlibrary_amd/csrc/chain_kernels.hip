@@ -6,8 +6,10 @@
 //        .align(crop=False)         tmlib/image.py:345-454  (shift + zero pad)
 //        .clip(clip_min, clip_max)  tmlib/image.py:570-597
 //        .scale(clip_min, clip_max) tmlib/image.py:493-568  (uint16 -> uint8 LUT)
-// before cutting pyramid tiles.  k_chain_u8 does all four in one pass that
-// reads the uint16 site (2 B/px) and writes the uint8 tile source (1 B/px).
+// before cutting pyramid tiles.  k_chain_u8t (any width: k_chain_u8_scalar)
+// does all four in one pass that reads the uint16 site (2 B/px) and writes the
+// uint8 tile source (1 B/px); k_fix_chain then refines in f64 the few pixels
+// whose f32 value is not safe to truncate.
 //
 // align is a window copy: the host evaluates the reference's numpy slicing
 // into (src_r0, src_c0, dst_r0, dst_c0, rows, cols); output pixels outside
@@ -19,7 +21,8 @@
 // trunc(double(i) * (255.0 / (n - 1))) with n = hi - lo, except the last one
 // (i = n - 1), which linspace sets to exactly 255, and n = 1 (a lone 0).  One
 // f64 multiply, bit-identical to the table (pinned exhaustively against the
-// reference's LUTs, tests/golden/map_uint8.npz).
+// reference's LUTs, tests/golden/map_uint8.npz).  k_chain_lut8 evaluates it
+// once per launch for all 65,536 values, clip included.
 #include "common.h"
 #include "correct_core.h"
 
@@ -83,16 +86,6 @@ __device__ __forceinline__ uint32_t correct16(uint32_t px, float mu, float a, co
   return (uint32_t)(int32_t)o & 0xFFFFu;
 }
 
-// Source-driven fused chain (W % 8 == 0): one thread = 8 consecutive SOURCE
-// pixels, their coefficients loaded once and reused for every site of its
-// part (blockIdx.y = site part).  align is a flat shift per site, off =
-// (dst_r0 - src_r0) * W + (dst_c0 - src_c0): source pixel p lands at p + off,
-// a bijection onto [off, npx + off), and source pixels outside the window land
-// outside the destination window (they write the padding value, 0 scaled).
-// The 8 result bytes of thread i go to [8i + off, 8i + off + 8); unless off
-// is a multiple of the 128-B line they are staged in LDS per workgroup and
-// stored as line-aligned 16-B chunks.  k_chain_fill pads [0, off) / [npx + off,
-// npx), the only destinations no source pixel reaches.
 // n < 8 bytes of v (low first) at the 8-aligned address p: dword, short, byte
 // pieces, each naturally aligned
 __device__ __forceinline__ void store_head(uint8_t* p, uint64_t v, int n) {
@@ -133,214 +126,58 @@ __device__ __forceinline__ int64_t xcd_tile(int64_t b, int64_t n) {
 }
 
 typedef float f32x2c_t __attribute__((ext_vector_type(2)));
-constexpr int kChainDepth = 4;
 
-// streamed-once site loads: non-temporal
-__device__ __forceinline__ uint4 ld_nt16(const uint4* p) {
-  typedef unsigned int u32x4n_t __attribute__((ext_vector_type(4)));
-  const u32x4n_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4n_t*>(p));
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-// LUT 0: clip + scale in f64 arithmetic; 1: the reference's uint8 table for
-// the clipped range [lo, hi] staged in LDS (hi - lo + 1 bytes), one ds_read_u8
-// per pixel after the clip; 2: clip and table for every 16-bit value (64 KB,
-// copied from lut8, k_chain_lut8), indexed by the cast's low half directly --
-// the pass is VALU-bound (~24 ops + 2 transcendentals per pixel), and this
-// drops the clip's max/min and the index subtract.  NT threads per workgroup.
-template <bool LOG, int LUT, int NT = 256>
-__global__ __launch_bounds__(NT) void k_chain_u8(const uint16_t* __restrict__ in,
-                                                  uint8_t* __restrict__ out, int H, int W,
-                                                  int64_t n_sites, int64_t per,
-                                                  const float2* __restrict__ coef_lin,
-                                                  const float4* __restrict__ mconst2,
-                                                  FixList fl,
-                                                  const tmh_window* __restrict__ win, int lo,
-                                                  int hi, int T, double step,
-                                                  const uint8_t* __restrict__ lut8) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t slut[];
-  if (LUT == 1) {
-    for (int i = threadIdx.x; i <= hi - lo; i += NT)
-      slut[i] = (uint8_t)(i >= T ? 255u : (uint32_t)((double)i * step));
-    __syncthreads();
-  } else if (LUT == 2) {
-    for (int i = threadIdx.x; i < 65536 / 16; i += NT)
-      reinterpret_cast<uint4*>(slut)[i] = reinterpret_cast<const uint4*>(lut8)[i];
-    __syncthreads();
-  }
-  const int64_t npx = (int64_t)H * W;
-  const int64_t ngroups = npx >> 3;
-  // XCD-aware tile order: workgroups go round-robin over the 8 XCDs, so give
-  // XCD x a contiguous run of tiles -- neighbouring tiles' shifted outputs
-  // share a 128-B line at their seam, and a seam inside one XCD's L2 merges
-  // instead of leaving two partial lines to write back.
-  const int64_t tile = xcd_tile(blockIdx.x, gridDim.x);
-  const int64_t g = tile * NT + threadIdx.x;
-  const bool live = g < ngroups;
-  const int lane = threadIdx.x & 63;
-  const bool top_lane = threadIdx.x == NT - 1 || g + 1 >= ngroups;  // no upper neighbour run
-  __shared__ uint64_t edge[NT / 64];
-  __shared__ __attribute__((aligned(16))) uint8_t stage[NT * 8 + 256];
-  const int64_t p0 = (live ? g : 0) * 8;
-  const int r = (int)(p0 / W), c0 = (int)(p0 % W);
-  const float4 m = mconst2[0];
-  const f32x2c_t M = {m.x, m.x};
-  f32x2c_t mu[4], a[4];
-  {
-    const float4* cf = reinterpret_cast<const float4*>(coef_lin + p0);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float4 v0 = live ? cf[k] : make_float4(0.f, 1.f, 0.f, 1.f);
-      mu[k] = (f32x2c_t){v0.x, v0.z};
-      a[k] = (f32x2c_t){v0.y, v0.w};
-    }
-  }
-  const int64_t s0 = (int64_t)blockIdx.y * per;
-  const int64_t s1 = s0 + per < n_sites ? s0 + per : n_sites;
-  const uint4* src = reinterpret_cast<const uint4*>(in) + (live ? g : 0);
-  // kChainDepth sites' loads in flight ahead of the one being processed
-  uint4 q[kChainDepth];
-#pragma unroll
-  for (int k = 0; k < kChainDepth; ++k)
-    q[k] = live && s0 + k < s1 ? ld_nt16(src + (s0 + k) * ngroups) : make_uint4(0, 0, 0, 0);
-  for (int64_t s = s0; s < s1; ++s) {
-    const uint4 cur = q[0];
-#pragma unroll
-    for (int k = 0; k + 1 < kChainDepth; ++k) q[k] = q[k + 1];
-    q[kChainDepth - 1] = live && s + kChainDepth < s1 ? ld_nt16(src + (s + kChainDepth) * ngroups)
-                                                      : make_uint4(0, 0, 0, 0);
-    const tmh_window w = win[s];  // uniform: scalar loads
-    const uint32_t wd[4] = {cur.x, cur.y, cur.z, cur.w};
-    f32x2c_t t[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      t[k].x = (float)(wd[k] & 0xFFFFu);
-      t[k].y = (float)(wd[k] >> 16);
-    }
-    if (LOG) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        t[k].x = __builtin_amdgcn_logf(__builtin_fmaxf(t[k].x, m.z));
-        t[k].y = __builtin_amdgcn_logf(__builtin_fmaxf(t[k].y, m.z));
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) t[k] = __builtin_elementwise_fma(t[k] - mu[k], a[k], M);
-    uint32_t o[8];
-    float mx = 0.0f;  // largest |result| of the 8 pixels: one compare against T per 8
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        float x = LOG ? __builtin_amdgcn_exp2f(t[k][h]) : t[k][h];
-        mx = __builtin_fmaxf(mx, __builtin_fabsf(x));
-        x = __builtin_fminf(x, 2147418112.0f);  // >= 2^31, inf, NaN -> low half 0 (x86)
-        if (!LOG) x = __builtin_fmaxf(x, -2147483648.0f);
-        const uint32_t v16 = (uint32_t)(int32_t)x & 0xFFFFu;
-        if (LUT == 2) {
-          o[2 * k + h] = slut[v16];
-        } else {
-          const uint32_t v = min(max(v16, (uint32_t)lo), (uint32_t)hi);  // np.clip
-          o[2 * k + h] = LUT ? (uint32_t)slut[v - (uint32_t)lo]
-                             : (v - (uint32_t)lo >= (uint32_t)T ? 255u
-                                                                : (uint32_t)((double)(v - lo) * step));
-        }
-      }
-    }
-    // rare: a pixel beyond the f32 bound flags its group of 8 for the f64
-    // refinement (common.h; f64 is the reference value for all 8)
-    if (mx >= m.w && live) fix_push8(fl, 0xFFu, s, p0);
-    // pixels outside the source window write the padding value: 0 after
-    // clip/scale (clip(0) = lo, the table's first entry is 0)
-    const int cs = c0 - w.src_c0;
-    int jlo = -cs < 0 ? 0 : (-cs > 8 ? 8 : -cs);
-    int jhi = w.cols - cs < 0 ? 0 : (w.cols - cs > 8 ? 8 : w.cols - cs);
-    if ((unsigned)(r - w.src_r0) >= (unsigned)w.rows) jhi = 0;
-    const uint64_t keep = jhi > jlo ? ((~0ull >> (8 * (8 - (jhi - jlo)))) << (8 * jlo)) : 0ull;
-    const uint32_t lo4 = (o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24)) & (uint32_t)keep;
-    const uint32_t hi4 = (o[4] | (o[5] << 8) | (o[6] << 16) | (o[7] << 24)) & (uint32_t)(keep >> 32);
-    const uint64_t v8 = ((uint64_t)hi4 << 32) | lo4;
-    const int64_t off = (int64_t)(w.dst_r0 - w.src_r0) * W + (w.dst_c0 - w.src_c0);
-    const int64_t D = p0 + off;  // destination of byte 0
-    const int rr = (int)(off & 7);  // uniform
-    uint8_t* o8 = out + s * npx;
-    if ((off & 127) == 0) {  // line-aligned destination: direct stores
-      if (live && D >= 0 && D < npx) *reinterpret_cast<uint64_t*>(o8 + D) = v8;
-      continue;
-    }
-    // Otherwise the workgroup's 2,048 output bytes [o0, o0 + 2048) are staged
-    // in LDS and leave as whole 16-B chunks of 128-B lines: a shifted run
-    // written lane by lane would split every wave's store across one more,
-    // partial line on each side.  Runs are first made 8-byte aligned with the
-    // upper neighbour's bytes (wave shuffle, LDS slot across waves).
-    const int wv = threadIdx.x >> 6;
-    if (lane == 0) edge[wv] = v8;
-    const uint32_t nlo = (uint32_t)__shfl_down((int)lo4, 1, 64);
-    const uint32_t nhi = (uint32_t)__shfl_down((int)hi4, 1, 64);
-    __syncthreads();  // (1) edge slots written; the previous site's stage is drained
-    uint64_t n8 = ((uint64_t)nhi << 32) | nlo;
-    if (lane == 63 && wv < NT / 64 - 1) n8 = edge[wv + 1];
-    const int64_t o0 = tile * NT * 8 + off;  // destination of thread 0's byte 0
-    const int64_t L0 = o0 >= 0 ? (o0 & ~(int64_t)127) : -((-o0 + 127) & ~(int64_t)127);
-    if (!live) {
-      // no run (past the last group): nothing to stage
-    } else if (rr == 0) {
-      *reinterpret_cast<uint64_t*>(stage + (D - L0)) = v8;
-    } else {
-      const int64_t A = D - rr + 8;  // aligned word holding our bytes [8 - rr, 8)
-      if (!top_lane) {
-        *reinterpret_cast<uint64_t*>(stage + (A - L0)) = (v8 >> (8 * (8 - rr))) | (n8 << (8 * rr));
-      } else {
-        for (int b = 8 - rr; b < 8; ++b) stage[D + b - L0] = (uint8_t)(v8 >> (8 * b));
-      }
-      if (threadIdx.x == 0)
-        for (int b = 0; b < 8 - rr; ++b) stage[D + b - L0] = (uint8_t)(v8 >> (8 * b));
-    }
-    __syncthreads();  // (2) stage complete
-    // valid destination bytes of this workgroup: [o0, o0 + 2048) within the
-    // site (the last workgroup may own fewer groups)
-    const int64_t wg_bytes = (ngroups - tile * NT < NT ? ngroups - tile * NT : NT) * 8;
-    const int64_t v0 = o0 > 0 ? o0 : 0;
-    const int64_t v1 = o0 + wg_bytes < npx ? o0 + wg_bytes : npx;
-    const int64_t c = L0 + 16 * (int64_t)threadIdx.x;  // this thread's 16-B chunk
-    if (c + 16 <= v1 && c >= v0) {
-      *reinterpret_cast<uint4*>(o8 + c) = *reinterpret_cast<const uint4*>(stage + (c - L0));
-    } else if (c < v1 && c + 16 > v0) {
-      for (int b = 0; b < 16; ++b)
-        if (c + b >= v0 && c + b < v1) o8[c + b] = stage[c + b - L0];
-    }
-  }
-}
-
-// The production chain pass: k_chain_u8's 16-bit-table form with its VALU
-// trimmed (the pass is VALU-bound: ~24 issue slots per pixel, two of them
-// quarter-rate transcendentals).
-//  * no queue of site loads (below);
-//  * a group flagged when its max |o| passes the f32 error bound of its
-//    largest a, |o| (K1 a_max8 + K2) >= 1 (the fused pass's per-pixel rule,
-//    fcorrect8, with the group's largest a), and k_fix_chain refines only the
-//    pixels beyond their own bound (the launch-wide T = 1 / (K1 a_max + K2)
-//    with whole groups refined ran 0.30 ms of f64 fixups per 3,456 bench
-//    sites);
+// The chain pass for W % 8 == 0, source-driven: one thread = 8 consecutive
+// SOURCE pixels (one 16-byte load per site), their coefficients loaded once
+// and reused for every site of its part (blockIdx.y = site part).  align is a
+// flat shift per site, off = (dst_r0 - src_r0) * W + (dst_c0 - src_c0): source
+// pixel p lands at p + off, a bijection onto [off, npx + off), and source
+// pixels outside the window land outside the destination window (they write
+// the padding value, 0 scaled).  The destinations no source pixel reaches,
+// [0, off) or [npx + off, npx), are padded by the first / last workgroup.
+//
+// clip + scale is one byte load: the reference's table for every 16-bit value
+// (k_chain_lut8, 64 KB) is copied into LDS and indexed by the cast's low half.
+// Workgroups have kChainThreads = 1,024 threads, two per CU beside the table
+// (smaller ones copy it too often: 256 threads ran 37 ms, 512 21.6, 1,024 14.6,
+// profiles/r2/mb_chain_lut64_r2lt.txt).
+//
+// The pass is VALU-bound (~24 issue slots per pixel, two of them quarter-rate
+// transcendentals), so the per-pixel work is trimmed:
+//  * a group is flagged for k_fix_chain when its max |o| passes the f32 error
+//    bound of its largest a, |o| (K1 a_max8 + K2) >= 1 (the fused pass's
+//    per-pixel rule, fcorrect8, with the group's largest a), and k_fix_chain
+//    refines only the pixels beyond their own bound (the launch-wide T =
+//    1 / (K1 a_max + K2) with whole groups refined ran 0.30 ms of f64 fixups
+//    per 3,456 bench sites);
 //  * no min/max before the cast: every |o| >= 1 / K2 (< 2^18) fails its own
-//    f32 bound and is refined in f64; k_fix_chain refines only the pixels
-//    beyond their own bound and keeps the streamed byte of the others, whose
-//    |o| < 0.998 / K2 < 2^18 -- there v_cvt_i32_f32 truncates exactly as the
-//    x86 cast does, so no clamp is needed; NaN converts to 0 on both;
+//    f32 bound and is refined in f64; the pixels that keep their streamed byte
+//    have |o| < 0.998 / K2 < 2^18 -- there v_cvt_i32_f32 truncates exactly as
+//    the x86 cast does, so no clamp is needed; NaN converts to 0 on both;
 //  * ZADD: a zero pixel's floor as x + zf instead of max(x, zf) -- two pixels
 //    per v_pk_add_f32; exact for zf < 2^-25 (x >= 1 plus zf rounds to x);
 //  * the table bytes packed with v_perm (3 per 4 bytes) instead of shifts,
 //    ors and a masking bitop;
 //  * the align window's byte mask only for threads whose 8 pixels are not all
 //    inside it (a divergent branch: whole waves skip it).
-template <bool LOG, bool ZADD, int NT, bool PF = false, bool GB = true, bool SEAM = false>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2 * NT / 256))) void k_chain_u8t(const uint16_t* __restrict__ in,
-                                                   uint8_t* __restrict__ out, int H, int W,
-                                                   int64_t n_sites, int64_t per,
-                                                   const float2* __restrict__ coef_lin,
-                                                   const float4* __restrict__ mconst2, FixList fl,
-                                                   const tmh_window* __restrict__ win,
-                                                   const uint8_t* __restrict__ lut8) {
+//
+// The 8 result bytes of thread i go to [8i + off, 8i + off + 8).  With off a
+// multiple of the 128-B line they are stored directly.  Otherwise a shifted
+// run written lane by lane would split every wave's store across one more,
+// partial line on each side, so runs are first made 8-byte aligned with the
+// upper lane's bytes (wave shuffle), the lines a wave covers alone are stored
+// as aligned 8-byte words, and the lines two waves (or two workgroups) share
+// -- the seams -- are assembled in LDS and stored as whole 16-B chunks.
+// Workgroups follow xcd_tile's order: neighbouring tiles' shifted outputs
+// share a line at their seam, and a seam inside one XCD's L2 merges instead of
+// leaving two partial lines to write back.
+constexpr int kChainThreads = 1024;
+template <bool LOG, bool ZADD>
+__global__ __launch_bounds__(kChainThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_chain_u8t(
+    const uint16_t* __restrict__ in, uint8_t* __restrict__ out, int H, int W, int64_t n_sites,
+    int64_t per, const float2* __restrict__ coef_lin, const float4* __restrict__ mconst2,
+    FixList fl, const tmh_window* __restrict__ win, const uint8_t* __restrict__ lut8) {
+  constexpr int NT = kChainThreads;
   extern __shared__ __attribute__((aligned(16))) uint8_t slut[];
   for (int i = threadIdx.x; i < 65536 / 16; i += NT)
     reinterpret_cast<uint4*>(slut)[i] = reinterpret_cast<const uint4*>(lut8)[i];
@@ -351,13 +188,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2 * NT / 256
   const int64_t g = tile * NT + threadIdx.x;
   const bool live = g < ngroups;
   const int lane = threadIdx.x & 63;
-  const bool top_lane = threadIdx.x == NT - 1 || g + 1 >= ngroups;
-  // SEAM: only the 128-B lines two waves share are staged (two sets, one
-  // barrier per site); otherwise the whole workgroup's bytes (k_chain_u8's
-  // staging, two barriers per site)
+  // two sets of seam lines used in turn: one barrier per site
   constexpr int kSeams = NT / 64 + 1;  // seam s = line L0 + 512 s
-  __shared__ uint64_t edge[SEAM ? 1 : NT / 64];
-  __shared__ __attribute__((aligned(16))) uint8_t stage[SEAM ? 2 * kSeams * 128 : NT * 8 + 256];
+  __shared__ __attribute__((aligned(16))) uint8_t stage[2 * kSeams * 128];
   const int64_t p0 = (live ? g : 0) * 8;
   const int r = (int)(p0 / W), c0 = (int)(p0 % W);
   const float4 m = mconst2[0];
@@ -428,7 +261,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2 * NT / 256
     uint32_t hi4 = __builtin_amdgcn_perm(__builtin_amdgcn_perm(o[7], o[6], 0x0c0c0400u),
                                          __builtin_amdgcn_perm(o[5], o[4], 0x0c0c0400u), 0x05040100u);
     asm volatile("" : "+v"(lo4), "+v"(hi4));  // keeps the packing here (no code is emitted)
-    if (mx >= (GB ? thr : m.w) && live) fix_push8(fl, 0xFFu, s, p0);
+    // rare: a group beyond its f32 bound is flagged for the f64 refinement
+    if (mx >= thr && live) fix_push8(fl, 0xFFu, s, p0);
     // pixels outside the source window write the padding value (0 after
     // clip/scale); only threads with a pixel outside build the byte mask
     const int cs = c0 - w.src_c0;
@@ -452,7 +286,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2 * NT / 256
     // the destinations no source pixel reaches -- [0, off) for off > 0,
     // [npx + off, npx) for off < 0, all outside the destination window -- take
     // the padding value, written by the site part's first / last workgroup
-    // (k_chain_fill's job for k_chain_u8)
     if ((off > 0 && tile == 0) || (off < 0 && tile == (int64_t)gridDim.x - 1)) {
       const int b0 = off > 0 ? 0 : n32 + off, b1 = off > 0 ? off : n32;
       const uint8_t pad = slut[0];
@@ -463,139 +296,79 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2 * NT / 256
       if (live && (unsigned)D < (unsigned)n32) *reinterpret_cast<uint64_t*>(o8 + D) = v8;
       return;
     }
-    if (SEAM) {
-      // A wave's 512 output bytes [o0 + 512 w, +512) fully cover the three
-      // lines L0 + 512 w + 128 k (k = 1..3): its lanes store their aligned
-      // 8-byte words there directly.  The lines L0 + 512 s (s = 0..16) are
-      // shared with the neighbouring wave (or workgroup): their words and the
-      // partial words at the waves' edges go to an LDS copy of those lines,
-      // stored after one barrier as whole 16-B chunks.
-      const int o0 = (int)(tile * NT * 8) + off;  // uniform
-      const int L0 = o0 & ~127;
-      uint8_t* seam = stage + (int)(s & 1) * (kSeams * 128);
-      const uint32_t nlo = (uint32_t)__shfl_down((int)lo4, 1, 64);
-      const uint32_t nhi = (uint32_t)__shfl_down((int)hi4, 1, 64);
-      const uint64_t n8 = ((uint64_t)nhi << 32) | nlo;
-      const bool wtop = lane == 63 || g + 1 >= ngroups;  // no upper neighbour in the wave
-      if (live) {
-        const int X = rr == 0 ? D : D - rr + 8;  // the aligned word this lane completes
-        const int r = X - L0;
-        const bool in_seam = (r & 511) < 128;
-        uint8_t* sp = seam + (r >> 9) * 128 + (r & 127);
-        if (rr == 0 || !wtop) {  // a whole word: ours, or our [8 - rr, 8) + the upper lane's [0, 8 - rr)
-          const uint64_t v = rr == 0 ? v8 : (v8 >> (8 * (8 - rr))) | (n8 << (8 * rr));
-          if (in_seam)
-            *reinterpret_cast<uint64_t*>(sp) = v;
-          else if ((unsigned)X < (unsigned)n32)
-            *reinterpret_cast<uint64_t*>(o8 + X) = v;
-        } else {  // the wave's top lane: only our bytes of that word
-          if (in_seam)
-            store_head(sp, v8 >> (8 * (8 - rr)), rr);
-          else if ((unsigned)X < (unsigned)n32)
-            store_head(o8 + X, v8 >> (8 * (8 - rr)), rr);
-        }
-        if (rr != 0 && lane == 0) {  // our bytes [0, 8 - rr): the top of word X - 8, a seam line
-          const int q = X - 8 - L0;
-          store_tail(seam + (q >> 9) * 128 + (q & 127) + 8, v8, 8 - rr);
-        }
-      }
-      __syncthreads();  // seam lines complete (the other set was read before it)
-      const int wg_bytes = (int)((ngroups - tile * NT < NT ? ngroups - tile * NT : NT) * 8);
-      const int v0 = o0 > 0 ? o0 : 0;
-      const int v1 = o0 + wg_bytes < n32 ? o0 + wg_bytes : n32;
-      if ((int)threadIdx.x < kSeams * 8) {
-        const int sl = threadIdx.x >> 3, ch = threadIdx.x & 7;
-        const int c = L0 + 512 * sl + 16 * ch;
-        const uint8_t* src8 = seam + sl * 128 + 16 * ch;
-        if (c + 16 <= v1 && c >= v0) {
-          *reinterpret_cast<uint4*>(o8 + c) = *reinterpret_cast<const uint4*>(src8);
-        } else if (c < v1 && c + 16 > v0) {
-          for (int b = 0; b < 16; ++b)
-            if (c + b >= v0 && c + b < v1) o8[c + b] = src8[b];
-        }
-      }
-      return;
-    }
-    // as k_chain_u8: the workgroup's output bytes staged in LDS and stored as
-    // whole 16-B chunks of 128-B lines (runs first made 8-byte aligned with the
-    // upper neighbour's bytes: wave shuffle, LDS slot across waves)
-    const int wv = threadIdx.x >> 6;
-    if (lane == 0) edge[wv] = v8;
-    const uint32_t nlo = (uint32_t)__shfl_down((int)lo4, 1, 64);
-    const uint32_t nhi = (uint32_t)__shfl_down((int)hi4, 1, 64);
-    __syncthreads();  // (1) edge slots written; the previous site's stage is drained
-    uint64_t n8 = ((uint64_t)nhi << 32) | nlo;
-    if (lane == 63 && wv < NT / 64 - 1) n8 = edge[wv + 1];
+    // A wave's 512 output bytes [o0 + 512 w, +512) fully cover the three
+    // lines L0 + 512 w + 128 k (k = 1..3): its lanes store their aligned
+    // 8-byte words there directly.  The lines L0 + 512 s (s = 0..16) are
+    // shared with the neighbouring wave (or workgroup): their words and the
+    // partial words at the waves' edges go to an LDS copy of those lines,
+    // stored after one barrier as whole 16-B chunks.
     const int o0 = (int)(tile * NT * 8) + off;  // uniform: destination of thread 0's byte 0
     const int L0 = o0 & ~127;                   // its line (floor, also for o0 < 0)
-    if (!live) {
-      // past the last group: nothing to stage
-    } else if (rr == 0) {
-      *reinterpret_cast<uint64_t*>(stage + (D - L0)) = v8;
-    } else {
-      const int A = D - rr + 8;  // aligned word holding our bytes [8 - rr, 8)
-      if (!top_lane) {
-        *reinterpret_cast<uint64_t*>(stage + (A - L0)) = (v8 >> (8 * (8 - rr))) | (n8 << (8 * rr));
-      } else {
-        for (int b = 8 - rr; b < 8; ++b) stage[D + b - L0] = (uint8_t)(v8 >> (8 * b));
+    uint8_t* seam = stage + (int)(s & 1) * (kSeams * 128);
+    const uint32_t nlo = (uint32_t)__shfl_down((int)lo4, 1, 64);
+    const uint32_t nhi = (uint32_t)__shfl_down((int)hi4, 1, 64);
+    const uint64_t n8 = ((uint64_t)nhi << 32) | nlo;
+    const bool wtop = lane == 63 || g + 1 >= ngroups;  // no upper neighbour in the wave
+    if (live) {
+      const int X = rr == 0 ? D : D - rr + 8;  // the aligned word this lane completes
+      const int r = X - L0;
+      const bool in_seam = (r & 511) < 128;
+      uint8_t* sp = seam + (r >> 9) * 128 + (r & 127);
+      if (rr == 0 || !wtop) {  // a whole word: ours, or our [8 - rr, 8) + the upper lane's [0, 8 - rr)
+        const uint64_t v = rr == 0 ? v8 : (v8 >> (8 * (8 - rr))) | (n8 << (8 * rr));
+        if (in_seam)
+          *reinterpret_cast<uint64_t*>(sp) = v;
+        else if ((unsigned)X < (unsigned)n32)
+          *reinterpret_cast<uint64_t*>(o8 + X) = v;
+      } else {  // the wave's top lane: only our bytes of that word
+        if (in_seam)
+          store_head(sp, v8 >> (8 * (8 - rr)), rr);
+        else if ((unsigned)X < (unsigned)n32)
+          store_head(o8 + X, v8 >> (8 * (8 - rr)), rr);
       }
-      if (threadIdx.x == 0)
-        for (int b = 0; b < 8 - rr; ++b) stage[D + b - L0] = (uint8_t)(v8 >> (8 * b));
+      if (rr != 0 && lane == 0) {  // our bytes [0, 8 - rr): the top of word X - 8, a seam line
+        const int q = X - 8 - L0;
+        store_tail(seam + (q >> 9) * 128 + (q & 127) + 8, v8, 8 - rr);
+      }
     }
-    __syncthreads();  // (2) stage complete
-    // valid destination bytes of this workgroup: [v0, v1) (uniform)
+    __syncthreads();  // seam lines complete (the other set was read before it)
+    // valid destination bytes of this workgroup: [v0, v1) (uniform; the last
+    // workgroup may own fewer groups)
     const int wg_bytes = (int)((ngroups - tile * NT < NT ? ngroups - tile * NT : NT) * 8);
     const int v0 = o0 > 0 ? o0 : 0;
     const int v1 = o0 + wg_bytes < n32 ? o0 + wg_bytes : n32;
-    const int c = L0 + 16 * (int)threadIdx.x;  // this thread's 16-B chunk
-    if (c + 16 <= v1 && c >= v0) {
-      *reinterpret_cast<uint4*>(o8 + c) = *reinterpret_cast<const uint4*>(stage + (c - L0));
-    } else if (c < v1 && c + 16 > v0) {
-      for (int b = 0; b < 16; ++b)
-        if (c + b >= v0 && c + b < v1) o8[c + b] = stage[c + b - L0];
+    if ((int)threadIdx.x < kSeams * 8) {
+      const int sl = threadIdx.x >> 3, ch = threadIdx.x & 7;
+      const int c = L0 + 512 * sl + 16 * ch;
+      const uint8_t* src8 = seam + sl * 128 + 16 * ch;
+      if (c + 16 <= v1 && c >= v0) {
+        *reinterpret_cast<uint4*>(o8 + c) = *reinterpret_cast<const uint4*>(src8);
+      } else if (c < v1 && c + 16 > v0) {
+        for (int b = 0; b < 16; ++b)
+          if (c + b >= v0 && c + b < v1) o8[c + b] = src8[b];
+      }
     }
   };
 
-  // one site's load, then its processing: k_chain_u8's queue of kChainDepth
-  // loads compiled to a full wait for the load just issued (a conditional load
-  // in the loop), i.e. this same order, plus 16 register moves per site; the
-  // 32 waves of a CU hide the latency.  (A pipeline that really keeps loads in
-  // flight across sites ran slower for this shape: 19.4 vs 14.5 ms,
-  // profiles/r3/mb_chain_pipeline_r3n.txt.)
-  if (PF) {  // the next site's load issued before this site's processing
-    if (s0 >= s1) return;
-    uint4 nxt = ld_nt16(src + s0 * ngroups);
-    for (int64_t s = s0; s < s1; ++s) {
-      const uint4 cur = nxt;
-      nxt = ld_nt16(src + (s + 1 < s1 ? s + 1 : s) * ngroups);  // unconditional
-      site(cur, s);
-    }
-  } else {
-    for (int64_t s = s0; s < s1; ++s)
-      site(live ? ld_nt16(src + s * ngroups) : make_uint4(0, 0, 0, 0), s);
+  // The next site's load is issued before this site's processing, and
+  // unconditionally (the last iteration reloads its own site): a load under a
+  // condition in the loop compiles to a full wait for the load just issued.
+  // The 32 waves of a CU hide the rest of the latency.  (A pipeline that keeps
+  // several sites' loads in flight ran slower for this shape: 19.4 vs 14.5
+  // ms, profiles/r3/mb_chain_pipeline_r3n.txt.)
+  if (s0 >= s1) return;
+  uint4 nxt = ld_nt(src + s0 * ngroups);
+  for (int64_t s = s0; s < s1; ++s) {
+    const uint4 cur = nxt;
+    nxt = ld_nt(src + (s + 1 < s1 ? s + 1 : s) * ngroups);
+    site(cur, s);
   }
 }
 
-// The 16-bit clip + scale table of k_chain_u8<LUT = 2>: entry v = scale8(clip(v)).
+// The 16-bit clip + scale table of k_chain_u8t: entry v = scale8(clip(v)).
 __global__ void k_chain_lut8(uint8_t* __restrict__ lut8, int lo, int hi, int T, double step) {
   const int v = (int)blockIdx.x * 256 + threadIdx.x;
   if (v < 65536) lut8[v] = (uint8_t)clip_scale8((uint32_t)v, lo, hi, T, step);
-}
-
-// The destinations no source pixel reaches: [0, off) for off > 0, [npx + off,
-// npx) for off < 0 (all outside the destination window).
-__global__ void k_chain_fill(uint8_t* __restrict__ out, int H, int W,
-                             const tmh_window* __restrict__ win, int lo, int hi, int T,
-                             double step) {
-  const int64_t npx = (int64_t)H * W;
-  const int64_t s = blockIdx.y;
-  const tmh_window w = win[s];
-  const int64_t off = (int64_t)(w.dst_r0 - w.src_r0) * W + (w.dst_c0 - w.src_c0);
-  const int64_t b0 = off > 0 ? 0 : npx + off, b1 = off > 0 ? off : npx;
-  const uint8_t pad = (uint8_t)clip_scale8(0u, lo, hi, T, step);
-  for (int64_t i = b0 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < b1;
-       i += (int64_t)gridDim.x * 256)
-    out[s * npx + i] = pad;
 }
 
 // Any width: one thread per output pixel.
@@ -1000,6 +773,7 @@ void launch_chain_u8(const uint16_t* in, uint8_t* out, int H, int W, int64_t n_s
                      const tmh_window* d_win, int lo, int hi, uint8_t* lut8, hipStream_t s,
                      double zero_log10) {
   if (n_sites <= 0) return;
+  TMH_CHECK(lut8 != nullptr, TMH_EINVAL, "launch_chain_u8: no table scratch");
   ProfScope prof("chain", s);
   const int64_t npx = (int64_t)H * W;
   const double step = scale_step(lo, hi);
@@ -1007,45 +781,21 @@ void launch_chain_u8(const uint16_t* in, uint8_t* out, int H, int W, int64_t n_s
   const bool vec = (W & 7) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 &&
                    (reinterpret_cast<uintptr_t>(out) & 7) == 0 && npx < ((int64_t)1 << 30);
   if (vec) {
-    // site parts even out the dispatch rounds (each thread streams its part)
-    const int64_t parts = n_sites >= 64 ? 8 : 1;
+    hipLaunchKernelGGL(k_chain_lut8, dim3(256), dim3(256), 0, s, lut8, lo, hi, T, step);
+    // site parts even out the dispatch rounds (each thread streams its part):
+    // 16 parts ran 3,456 sites of 2160x2560 in 12.49 ms against 12.77 with 8
+    // (tools/mb/mb_chain.hip)
+    const int64_t parts = n_sites >= 128 ? 16 : n_sites >= 64 ? 8 : 1;
     const int64_t per = cdiv(n_sites, parts);
-    const int lut_bytes = hi - lo + 1;
-    const bool lut = lut_bytes <= 16384;  // else three f64 ops per pixel
-    const size_t shm = lut ? (size_t)((lut_bytes + 15) & ~15) : 0;
-#define TMH_CHAIN(L_, U_, NT_, SHM_, LUT8_)                                                      \
-  hipLaunchKernelGGL((k_chain_u8<L_, U_, NT_>),                                                  \
-                     dim3((unsigned)cdiv(npx >> 3, NT_), (unsigned)cdiv(n_sites, per)), dim3(NT_), \
-                     SHM_, s, in, out, H, W, n_sites, per, coef_lin, mconst2, fl, d_win, lo, hi, T,  \
-                     step, LUT8_)
-    if (lut8) {
-      // the whole 16-bit table: 1,024-thread workgroups (two per CU with the
-      // 64 KB table; smaller ones copy it too often: 256 threads ran 37 ms,
-      // 512 21.6, 1,024 14.6 against 15.0 for the clipped-range table,
-      // profiles/r2/mb_chain_lut64_r2lt.txt)
-      hipLaunchKernelGGL(k_chain_lut8, dim3(256), dim3(256), 0, s, lut8, lo, hi, T, step);
-      // 16 site parts: 3,456 sites of 2160x2560 ran 12.49 ms against 12.77
-      // with 8 (tools/mb/mb_chain.hip)
-      const int64_t tparts = n_sites >= 128 ? 16 : parts, tper = cdiv(n_sites, tparts);
-      const dim3 grid((unsigned)cdiv(npx >> 3, 1024), (unsigned)cdiv(n_sites, tper));
+    const dim3 grid((unsigned)cdiv(npx >> 3, kChainThreads), (unsigned)cdiv(n_sites, per));
 #define TMH_CHAIN_T(L_, Z_)                                                                      \
-  hipLaunchKernelGGL((k_chain_u8t<L_, Z_, 1024, true, true, true>), grid, dim3(1024), 65536, s, \
-                     in, out, H, W, n_sites, tper, coef_lin, mconst2, fl, d_win, lut8)
-      // zf = 10**zero_log10 below 2^-25 (~2.98e-8): the floor as an add is exact
-      if (!log_transform) TMH_CHAIN_T(false, false);
-      else if (zero_log10 <= -8.0) TMH_CHAIN_T(true, true);
-      else TMH_CHAIN_T(true, false);
+  hipLaunchKernelGGL((k_chain_u8t<L_, Z_>), grid, dim3(kChainThreads), 65536, s, in, out, H, W, \
+                     n_sites, per, coef_lin, mconst2, fl, d_win, lut8)
+    // zf = 10**zero_log10 below 2^-25 (~2.98e-8): the floor as an add is exact
+    if (!log_transform) TMH_CHAIN_T(false, false);
+    else if (zero_log10 <= -8.0) TMH_CHAIN_T(true, true);
+    else TMH_CHAIN_T(true, false);
 #undef TMH_CHAIN_T
-    } else {
-      if (log_transform) {
-        if (lut) TMH_CHAIN(true, 1, 256, shm, nullptr); else TMH_CHAIN(true, 0, 256, shm, nullptr);
-      } else {
-        if (lut) TMH_CHAIN(false, 1, 256, shm, nullptr); else TMH_CHAIN(false, 0, 256, shm, nullptr);
-      }
-      hipLaunchKernelGGL(k_chain_fill, dim3(64, (unsigned)n_sites), dim3(256), 0, s, out, H, W,
-                         d_win, lo, hi, T, step);
-    }
-#undef TMH_CHAIN
   } else {
     const dim3 grid((unsigned)cdiv(npx, 256));
     if (log_transform)

@@ -150,6 +150,28 @@ __device__ __forceinline__ int32_t correct_ref_f64(uint32_t x, double mean, doub
   return (t > -2147483649.0 && t < 2147483648.0) ? (int32_t)t : INT32_MIN;
 }
 
+// 16-byte non-temporal loads and stores: data streamed once (sites in, sites
+// out), kept out of L2's way.
+typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 ld_nt(const uint4* p) {
+  const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void st_nt(uint4* p, uint4 v) {
+  const u32x4_t w = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(w, reinterpret_cast<u32x4_t*>(p));
+}
+// A site pointer read from a block table is a generic pointer: the compiler
+// then emits flat loads (slower than global loads, and counted on both the
+// vector-memory and LDS counters).  Site loads through a global-address-space
+// pointer stay global_load.
+typedef __attribute__((address_space(1))) const u32x4_t gsite_t;
+__device__ __forceinline__ gsite_t* to_global(const void* p) { return (gsite_t*)p; }
+__device__ __forceinline__ uint4 ld_nt(gsite_t* p) {
+  const u32x4_t v = __builtin_nontemporal_load(p);
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+
 // launches (defined in the .hip files) -------------------------------------------
 // part: optional scratch of part_cap doubles for site-split launches (null: one part)
 // forced_parts: 0 = pick the site split automatically, 1..4 = that many parts
@@ -187,7 +209,7 @@ __device__ __forceinline__ int64_t site_in_block(const SiteTab& t, int64_t s) {
 void launch_welford(const uint16_t* sites, int64_t npx, int64_t n_sites, int64_t n0, double* rn,
                     double* mean, double* m2, const double* lut, int log_transform,
                     double* part, size_t part_cap, int forced_parts,
-                    unsigned long long* wide, int bright, hipStream_t s, int shape = -1,
+                    unsigned long long* wide, int bright, hipStream_t s,
                     const SiteTab& tab = SiteTab{});
 // Site probe: out[0] = 8-pixel groups sampled (kProbeGroups, spread over the
 // launch's first <= 64 sites), out[1] / out[2] = those holding a value >=
@@ -422,7 +444,7 @@ void launch_align(const void* in, void* out, int elem_bytes, int64_t n_sites, in
                   int ow, const tmh_window* d_win, hipStream_t s);
 void launch_map_u8(const uint16_t* in, uint8_t* out, int64_t n, int lo, int hi, hipStream_t s);
 // (launches its own fixup kernel after the chain pass; lut8: 64 KB of device
-// scratch for the 16-bit clip + scale table, or null for the clipped-range one)
+// scratch for the 16-bit clip + scale table, required)
 void launch_chain_u8(const uint16_t* in, uint8_t* out, int H, int W, int64_t n_sites,
                      const float2* coef_lin, const float4* mconst2, const FixList& fl,
                      const double2* coef64, const RefineConst* rc, int log_transform,

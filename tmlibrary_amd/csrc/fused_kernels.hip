@@ -168,18 +168,6 @@ __device__ __forceinline__ uint32_t far_mask(const float4 (&k)[4], const float (
   return far;
 }
 
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint4 ld_nt(const uint4* p) {
-  const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ void st_nt(uint4* p, uint4 v) {
-  const u32x4_t w = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(w, reinterpret_cast<u32x4_t*>(p));
-}
-
 __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {

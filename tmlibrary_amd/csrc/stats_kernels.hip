@@ -35,55 +35,35 @@ namespace tmh {
 // values (bright sites) use the same LUT on their top bits:
 //   u = 16 a + r,  a = u >> 4 in [256, 4096),
 //   log10(u) = log10(a) + log10(16) + log1p(t) / ln 10,  t = r / (16 a) < 1/256.
-// INV 0 / 1: 1/(16 a) in f64 (Newton step / LDS table) and a 5-term f64 series
-// (truncation below 3e-16 absolute), ~12 f64 ops.  INV 2 (production): the
-// small term log1p(t) / ln 10 <= 1.6e-3 in f32 -- rcp, three-term series
-// (truncation <= t^4/4 / ln 10 < 5e-11), f32 rounding < 2e-10 absolute -- then
-// one f64 add: a value >= 4,096 is within 3e-10 of numpy's log10 (1e-10
-// relative, against the 1e-6 bar on mean and std), at a fraction of the
-// VALU cost -- bright sites (most values >= 4,096) made the f64 form's pass
-// VALU-bound (17.7 ms vs 6.0 on standard sites, profiles/r2/ab_finalize_sr_r2y.jsonl).
+// The small term log1p(t) / ln 10 <= 1.6e-3 is taken in f32 -- rcp, three-term
+// series (truncation <= t^4/4 / ln 10 < 5e-11), f32 rounding < 2e-10 absolute
+// -- then one f64 add: a value >= 4,096 is within 3e-10 of numpy's log10 (1e-10
+// relative, against the 1e-6 bar on mean and std).  (An f64 reciprocal and
+// five-term series, ~12 f64 ops, made the pass VALU-bound on bright sites,
+// where most values are >= 4,096: 17.7 ms vs 6.0 on standard sites,
+// profiles/r2/ab_finalize_sr_r2y.jsonl.)
 constexpr double kInvLn10 = 0.43429448190325182765;
 constexpr double kLog10_16 = 1.2041199826559247809;
-constexpr int kWfInvScalar = 2;  // rare-value form of the odd-shape (per-pixel) pass
-// 1/(16 a): INV = 1 from the LDS table, INV = 0 by v_rcp_f32 plus one f64
-// Newton step (relative error ~1e-14: t then carries < 1e-17 absolute)
-template <int INV>
-__device__ __forceinline__ double recip16(uint32_t a, const double* sinv) {
-  if (INV == 1) return sinv[a];
-  const double d = (double)(a << 4);
-  const double r0 = (double)__builtin_amdgcn_rcpf((float)(a << 4));
-  return fma(r0, fma(-d, r0, 1.0), r0);
-}
-template <int INV>
-__device__ __forceinline__ double log10_big(uint32_t u, const double* slut, const double* sinv) {
+__device__ __forceinline__ double log10_big(uint32_t u, const double* slut) {
   const uint32_t a = u >> 4;
-  if (INV == 2) {
-    constexpr float c1 = (float)kInvLn10, c2 = (float)(-0.5 * kInvLn10),
-                    c3 = (float)(kInvLn10 / 3.0);
-    const float t = (float)(u & 15u) * __builtin_amdgcn_rcpf((float)(a << 4));
-    const float c = t * __builtin_fmaf(t, __builtin_fmaf(t, c3, c2), c1);
-    return slut[a] + (kLog10_16 + (double)c);
-  }
-  const double t = (double)(u & 15u) * recip16<INV>(a, sinv);
-  const double series =
-      t * (kInvLn10 +
-           t * (-0.5 * kInvLn10 + t * (kInvLn10 / 3.0 + t * (-0.25 * kInvLn10 + t * (0.2 * kInvLn10)))));
-  return (slut[a] + kLog10_16) + series;
+  constexpr float c1 = (float)kInvLn10, c2 = (float)(-0.5 * kInvLn10),
+                  c3 = (float)(kInvLn10 / 3.0);
+  const float t = (float)(u & 15u) * __builtin_amdgcn_rcpf((float)(a << 4));
+  const float c = t * __builtin_fmaf(t, __builtin_fmaf(t, c3, c2), c1);
+  return slut[a] + (kLog10_16 + (double)c);
 }
 
-// LUT entries staged in LDS: the 4,096 values below 2^12 (32 KB) and, with
-// INV = 1, the 4,096 reciprocals 1/(16 a) (32 KB more), so a site's 8 pixels
-// need the rare path exactly when one of their 16-bit words has a bit >= 12
-// set (one OR/AND over the four packed words).
+// LUT entries staged in LDS: the 4,096 values below 2^12 (32 KB), so a site's
+// 8 pixels need the rare path exactly when one of their 16-bit words has a
+// bit >= 12 set (one OR/AND over the four packed words).
 constexpr int kWfLut = 4096;
 
 // The fill issues up to 8 of a thread's loads before its LDS stores (one L2
 // round trip per 8 entries instead of one per entry: a 1,024-thread bright
 // workgroup, alone on its CU, waits out its whole fill).
-template <int INV, int LUTN = kWfLut>
+template <int LUTN = kWfLut>
 __device__ __forceinline__ void fill_wf_tables(const double* __restrict__ lut, double* slut,
-                                               double* sinv, int nt) {
+                                               int nt) {
   constexpr int U = 8;
   for (int i0 = threadIdx.x; i0 < LUTN; i0 += U * nt) {
     double v[U];
@@ -96,13 +76,12 @@ __device__ __forceinline__ void fill_wf_tables(const double* __restrict__ lut, d
     for (int u = 0; u < U; ++u) {
       const int i = i0 + u * nt;
       if (i < LUTN) slut[i] = v[u];
-      if (INV == 1 && i < kWfLut) sinv[i] = i ? 1.0 / (16.0 * (double)i) : 0.0;
     }
   }
 }
 
 // Bright sites: the host LUT's first kWfLutBright entries (160 KB of LDS less
-// the pass's two counters and reciprocal slot, one 1,024-thread workgroup per
+// 64 bytes, which hold the pass's two counters; one 1,024-thread workgroup per
 // CU) -- values below it take the exact table like the standard pass's values
 // below 4,096, and only the bright pixels above it the log10_big path (with
 // 4,096 entries most bright pixels took it: the pass was VALU-bound, 11.3-12.3
@@ -117,7 +96,7 @@ template <bool LOG>
 __device__ __forceinline__ double xform(uint32_t u, const double* slut) {
   if (!LOG) return (double)u;
   double x = slut[u & (uint32_t)(kWfLut - 1)];
-  if (u >= (uint32_t)kWfLut) x = log10_big<kWfInvScalar>(u, slut, nullptr);
+  if (u >= (uint32_t)kWfLut) x = log10_big(u, slut);
   return x;
 }
 
@@ -127,11 +106,11 @@ __device__ __forceinline__ void welford1(double x, double rn, double& mu, double
   m2 = fma(d, x - mu, m2);      // M2 + delta * (x - mean_new)
 }
 
-// Production shape of the vec8 pass: threads per workgroup and the
-// reciprocal source (tools/mb/mb_welford.hip compares the four shapes on
-// standard and bright sites; profiles/r2/mb_welford_shapes_*.txt).
+// Shape of the vec8 pass: threads per workgroup and sites per pipeline stage
+// (256 and 512 threads and 2, 3 and 4 sites per stage were measured on
+// standard and bright sites: profiles/r2/mb_welford_std_r2za.txt,
+// mb_welford_bright_r2za.txt, profiles/r3/mb_welford_r3h.txt).
 constexpr int kWfThreads = 256;
-constexpr int kWfInv = 2;
 constexpr int kWfScalarThreads = 256;
 constexpr int kWfGroup = 2;  // sites per pipeline stage (two stages in flight)
 constexpr int kWfMaxParts = 4;
@@ -179,9 +158,9 @@ __device__ __forceinline__ double lds_at(const double* base, uint32_t byte_off) 
 // recomputed with log10_big (wc counts the groups with a value >= 4,096, xc
 // those with a value >= 16,384: diagnostics since round 5).  The inner loop is VALU-issue bound (3 f64 ops per
 // pixel), so the integer work per pixel is kept to the gather address.
-template <bool LOG, int INV, int LUTN = kWfLut>
-__device__ __forceinline__ void xform8(const uint4 v, const double* slut, const double* sinv,
-                                       double (&x)[8], uint32_t& wc, uint32_t& xc) {
+template <bool LOG, int LUTN = kWfLut>
+__device__ __forceinline__ void xform8(const uint4 v, const double* slut, double (&x)[8],
+                                       uint32_t& wc, uint32_t& xc) {
   const uint32_t u[8] = {v.x & 0xFFFFu, v.x >> 16, v.y & 0xFFFFu, v.y >> 16,
                          v.z & 0xFFFFu, v.z >> 16, v.w & 0xFFFFu, v.w >> 16};
   const uint32_t any = v.x | v.y | v.z | v.w;
@@ -207,7 +186,7 @@ __device__ __forceinline__ void xform8(const uint4 v, const double* slut, const 
     if ((mx & 0xFFFFu) > kIdx || (mx >> 16) > kIdx) {  // a value beyond the table
 #pragma unroll
       for (int k = 0; k < 8; ++k)
-        if (u[k] > kIdx) x[k] = log10_big<INV>(u[k], slut, sinv);
+        if (u[k] > kIdx) x[k] = log10_big(u[k], slut);
     }
   } else if (LOG) {
     if (wide) {
@@ -217,7 +196,7 @@ __device__ __forceinline__ void xform8(const uint4 v, const double* slut, const 
       // one such value, and a branch-free pass over all eight cost 0.2 ms
 #pragma unroll
       for (int k = 0; k < 8; ++k)
-        if (u[k] > kIdx) x[k] = log10_big<INV>(u[k], slut, sinv);
+        if (u[k] > kIdx) x[k] = log10_big(u[k], slut);
     }
   } else {
     wc += wide ? 1u : 0u;
@@ -246,42 +225,24 @@ struct WfMerge {
 // blockIdx.y = site part: part p covers sites [p * per, min((p + 1) * per, n));
 // with more than one part each writes its (mean_l, M2_l) to `part` planes and
 // k_wf_merge_parts folds them in part order.
-// site loads: NTL = non-temporal (streamed once, kept out of L2's way)
-template <bool NTL>
-__device__ __forceinline__ uint4 ld_site(const uint4* p) {
-  if (!NTL) return *p;
-  typedef unsigned int u32x4w_t __attribute__((ext_vector_type(4)));
-  const u32x4w_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4w_t*>(p));
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-// A site pointer read from a block table is a generic pointer: the compiler
-// then emits flat loads (slower than global loads, and counted on both the
-// vector-memory and LDS counters).  Site loads through a global-address-space
-// pointer stay global_load.
-typedef unsigned int u32x4g_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const u32x4g_t gsite_t;
-__device__ __forceinline__ gsite_t* to_global(const void* p) { return (gsite_t*)p; }
-template <bool NTL>
-__device__ __forceinline__ uint4 ld_site(gsite_t* p) {
-  const u32x4g_t v = NTL ? __builtin_nontemporal_load(p) : *p;
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
+// Site loads are non-temporal (ld_nt, common.h: streamed once; regular loads
+// measured 6.60-6.75 vs 6.19-6.34 ms at job level,
+// profiles/r1/ab_welford_ntl.txt).
 
 // BLK: blocked site layout (common.h SiteTab): site t of the launch is site
 // t & (2^shift - 1) of block t >> shift; the block base is re-read (one scalar
 // load) only when the walk enters a new block.
-template <bool LOG, bool NTL, int NT, int INV, bool BLK = false, int G = kWfGroup,
-          int LUTN = kWfLut>
+template <bool LOG, int NT, bool BLK, int LUTN>
 __global__ __launch_bounds__(NT) void k_welford_vec8(
     const uint16_t* __restrict__ sites, int64_t npx, int64_t n_total, int64_t per,
     const WfMerge mg, double* __restrict__ mean, double* __restrict__ m2,
     const double* __restrict__ lut, double* __restrict__ part,
     unsigned long long* __restrict__ wide, const SiteTab tab) {
   const int parts = (int)gridDim.y;
-  __shared__ double slut[LUTN], sinv[INV == 1 ? kWfLut : 1];
+  constexpr int G = kWfGroup;
+  __shared__ double slut[LUTN];
   __shared__ uint32_t wide_sh[2];
-  if (LOG) fill_wf_tables<INV, LUTN>(lut, slut, sinv, NT);
+  if (LOG) fill_wf_tables<LUTN>(lut, slut, NT);
   if (threadIdx.x < 2) wide_sh[threadIdx.x] = 0u;
   __syncthreads();
   const int64_t ngroups = npx >> 3;
@@ -315,10 +276,10 @@ __global__ __launch_bounds__(NT) void k_welford_vec8(
   // current group is folded in (tail loads clamp to the last site: harmless)
   uint4 cur[G], nxt[G];
 #pragma unroll
-  for (int k = 0; k < G; ++k) cur[k] = ld_site<NTL>(site(k < last ? k : last));
+  for (int k = 0; k < G; ++k) cur[k] = ld_nt(site(k < last ? k : last));
   double K[8], s1[8], s2[8];
   uint32_t wc = 0, xc = 0;  // this thread's groups with a value >= 4,096 / >= 16,384
-  xform8<LOG, INV, LUTN>(cur[0], slut, sinv, K, wc, xc);
+  xform8<LOG, LUTN>(cur[0], slut, K, wc, xc);
   wc = xc = 0;
 #pragma unroll
   for (int k = 0; k < 8; ++k) s1[k] = s2[k] = 0.0;
@@ -333,7 +294,7 @@ __global__ __launch_bounds__(NT) void k_welford_vec8(
     for (int k = 0; k < G; ++k) {
       if (s + k < ns) {
         double x[8];
-        xform8<LOG, INV, LUTN>(v[k], slut, sinv, x, wc, xc);
+        xform8<LOG, LUTN>(v[k], slut, x, wc, xc);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const double d = x[j] - K[j];
@@ -347,7 +308,7 @@ __global__ __launch_bounds__(NT) void k_welford_vec8(
 #pragma unroll
     for (int k = 0; k < G; ++k) {
       const int t = s + k;
-      v[k] = ld_site<NTL>(site(t < (int)last ? t : (int)last));
+      v[k] = ld_nt(site(t < (int)last ? t : (int)last));
     }
   };
   for (int s = 0; s < ns; s += 2 * G) {
@@ -451,7 +412,7 @@ __global__ __launch_bounds__(kWfScalarThreads) void k_welford_scalar(
     const double* __restrict__ rn, double* __restrict__ mean, double* __restrict__ m2,
     const double* __restrict__ lut) {
   __shared__ double slut[kWfLut];
-  if (LOG) fill_wf_tables<0>(lut, slut, nullptr, kWfScalarThreads);
+  if (LOG) fill_wf_tables(lut, slut, kWfScalarThreads);
   __syncthreads();
   const int64_t p = (int64_t)blockIdx.x * kWfScalarThreads + threadIdx.x;
   if (p >= npx) return;
@@ -478,30 +439,18 @@ static int welford_parts(int64_t n_sites, int64_t npx, size_t part_cap, int forc
   return forced && fits(forced) ? forced : 1;
 }
 
-template <int NT, int INV, int G = kWfGroup, int LUTN = kWfLut>
+template <bool LOG, int NT, int LUTN>
 static void launch_welford_vec8(const uint16_t* sites, int64_t npx, int64_t n_sites, int64_t per,
                                 int f, const WfMerge& mg, double* mean, double* m2,
-                                const double* lut, int log_transform, double* part,
-                                unsigned long long* wide, hipStream_t s,
-                                const SiteTab& tab = SiteTab{}) {
+                                const double* lut, double* part, unsigned long long* wide,
+                                hipStream_t s, const SiteTab& tab) {
   const dim3 grid((unsigned)cdiv(npx >> 3, NT), (unsigned)f);
-  // site loads are non-temporal (streamed once; regular loads measured
-  // 6.60-6.75 vs 6.19-6.34 ms at job level, profiles/r1/ab_welford_ntl.txt)
-#define TMH_WF(L_, B_)                                                                           \
-  hipLaunchKernelGGL((k_welford_vec8<L_, true, NT, INV, B_, G, LUTN>), grid, dim3(NT), 0, s,     \
-                     sites, npx, n_sites, per, mg, mean, m2, lut, part, wide, tab)
-  if (tab.in) {
-    if (log_transform)
-      TMH_WF(true, true);
-    else
-      TMH_WF(false, true);
-  } else {
-    if (log_transform)
-      TMH_WF(true, false);
-    else
-      TMH_WF(false, false);
-  }
-#undef TMH_WF
+  if (tab.in)
+    hipLaunchKernelGGL((k_welford_vec8<LOG, NT, true, LUTN>), grid, dim3(NT), 0, s, sites, npx,
+                       n_sites, per, mg, mean, m2, lut, part, wide, tab);
+  else
+    hipLaunchKernelGGL((k_welford_vec8<LOG, NT, false, LUTN>), grid, dim3(NT), 0, s, sites, npx,
+                       n_sites, per, mg, mean, m2, lut, part, wide, tab);
 }
 
 // Site probe of a job (tmh_stats' automatic choices, abi.hip): of kProbeGroups
@@ -561,52 +510,37 @@ void launch_site_probe(const uint16_t* sites, int64_t npx, int64_t n_sites, unsi
   TMH_HIP(hipGetLastError());
 }
 
-// shape = -1: production (kWfThreads, kWfInv); 0..8: (256|512 threads) x
-// (f64 Newton | f64 LDS-table reciprocal | f32 small term) x pipeline depth,
-// for the microbenchmark.  bright (production shape, log transform, no forced
-// split): the host's site probe found bright sites -- the kWfLutBright-entry
-// (20,472: 160 KB) LUT pass in kWfBrightParts site parts (the log10 pass is
-// VALU-bound there: three times the workgroups even the dispatch rounds, 11.3
-// vs 12.4 ms with the 4,096-entry pass, profiles/r2/mb_welford_bright_r2za.txt;
-// round 3's 16,384 entries 8.0 vs 11.4 ms,
-// profiles/r3/ab_welford_bright16k_bright_r3m.jsonl).
+// bright (log transform, no forced split): the host's site probe found bright
+// sites -- the kWfLutBright-entry (20,472: 160 KB) LUT pass in kWfBrightParts
+// site parts (the log10 pass is VALU-bound there: three times the workgroups
+// even the dispatch rounds, 11.3 vs 12.4 ms with the 4,096-entry pass,
+// profiles/r2/mb_welford_bright_r2za.txt; round 3's 16,384 entries 8.0 vs 11.4
+// ms, profiles/r3/ab_welford_bright16k_bright_r3m.jsonl).
 void launch_welford(const uint16_t* sites, int64_t npx, int64_t n_sites, int64_t n0, double* rn,
                     double* mean, double* m2, const double* lut, int log_transform,
                     double* part, size_t part_cap, int forced_parts,
-                    unsigned long long* wide, int bright, hipStream_t s, int shape,
-                    const SiteTab& tab) {
+                    unsigned long long* wide, int bright, hipStream_t s, const SiteTab& tab) {
   if (n_sites <= 0) return;
   // (a blocked layout is checked by the caller: npx % 8 == 0, 16-B aligned blocks)
   const bool vec = tab.in || ((npx & 7) == 0 && (reinterpret_cast<uintptr_t>(sites) & 15) == 0);
   if (vec) {
     int f = part ? welford_parts(n_sites, npx, part_cap, forced_parts) : 1;
-    const bool bpass = bright > 0 && part && !forced_parts && log_transform && shape < 0 &&
+    const bool bpass = bright > 0 && part && !forced_parts && log_transform &&
                        welford_parts(n_sites, npx, part_cap, kWfBrightParts) == kWfBrightParts;
     if (bpass) f = kWfBrightParts;
     const int64_t per = cdiv(n_sites, f);
     const double nl = (double)n_sites, n = (double)(n0 + n_sites);
     const WfMerge mg{1.0 / nl, nl / n, (double)n0 * nl / n, n0 == 0};
     ProfScope prof("welford", s);  // the pass (and its part merge) only
-    switch (shape) {
-      case 0: launch_welford_vec8<256, 0>(sites, npx, n_sites, per, f, mg, mean, m2, lut, log_transform, part, wide, s); break;
-      case 1: launch_welford_vec8<256, 1>(sites, npx, n_sites, per, f, mg, mean, m2, lut, log_transform, part, wide, s); break;
-      case 2: launch_welford_vec8<512, 0>(sites, npx, n_sites, per, f, mg, mean, m2, lut, log_transform, part, wide, s); break;
-      case 3: launch_welford_vec8<512, 1>(sites, npx, n_sites, per, f, mg, mean, m2, lut, log_transform, part, wide, s); break;
-      case 4: launch_welford_vec8<256, 2>(sites, npx, n_sites, per, f, mg, mean, m2, lut, log_transform, part, wide, s); break;
-      case 5: launch_welford_vec8<512, 2>(sites, npx, n_sites, per, f, mg, mean, m2, lut, log_transform, part, wide, s); break;
-      // pipeline depth: sites per stage (two stages in flight)
-      case 6: launch_welford_vec8<256, 2, 3>(sites, npx, n_sites, per, f, mg, mean, m2, lut, log_transform, part, wide, s); break;
-      case 7: launch_welford_vec8<256, 2, 4>(sites, npx, n_sites, per, f, mg, mean, m2, lut, log_transform, part, wide, s); break;
-      case 8: launch_welford_vec8<512, 2, 4>(sites, npx, n_sites, per, f, mg, mean, m2, lut, log_transform, part, wide, s); break;
-      default:
-        if (bpass)
-          launch_welford_vec8<kWfThreadsBright, kWfInv, kWfGroup, kWfLutBright>(
-              sites, npx, n_sites, per, f, mg, mean, m2, lut, log_transform, part, wide, s, tab);
-        else
-          launch_welford_vec8<kWfThreads, kWfInv>(sites, npx, n_sites, per, f, mg, mean, m2, lut,
-                                                  log_transform, part, wide, s, tab);
-        break;
-    }
+    if (bpass)  // implies log_transform
+      launch_welford_vec8<true, kWfThreadsBright, kWfLutBright>(sites, npx, n_sites, per, f, mg,
+                                                                mean, m2, lut, part, wide, s, tab);
+    else if (log_transform)
+      launch_welford_vec8<true, kWfThreads, kWfLut>(sites, npx, n_sites, per, f, mg, mean, m2, lut,
+                                                    part, wide, s, tab);
+    else
+      launch_welford_vec8<false, kWfThreads, kWfLut>(sites, npx, n_sites, per, f, mg, mean, m2,
+                                                     lut, part, wide, s, tab);
     if (f > 1) {
       WfParts pc{};
       pc.n = f;
@@ -686,15 +620,15 @@ __global__ __launch_bounds__(kHistThreads) void k_hist_scatter(
     const int64_t n16 = npx >> 3;
     int64_t i = tid;
     for (; i + 3 * kHistThreads < n16; i += 4 * kHistThreads) {
-      const uint4 v0 = ld_site<true>(src + i), v1 = ld_site<true>(src + i + kHistThreads),
-                  v2 = ld_site<true>(src + i + 2 * kHistThreads),
-                  v3 = ld_site<true>(src + i + 3 * kHistThreads);
+      const uint4 v0 = ld_nt(src + i), v1 = ld_nt(src + i + kHistThreads),
+                  v2 = ld_nt(src + i + 2 * kHistThreads),
+                  v3 = ld_nt(src + i + 3 * kHistThreads);
       count8(v0, bins, himask, hhi);
       count8(v1, bins, himask, hhi);
       count8(v2, bins, himask, hhi);
       count8(v3, bins, himask, hhi);
     }
-    for (; i < n16; i += kHistThreads) count8(ld_site<true>(src + i), bins, himask, hhi);
+    for (; i < n16; i += kHistThreads) count8(ld_nt(src + i), bins, himask, hhi);
   } else {
     for (int64_t i = tid; i < npx; i += kHistThreads) {
       const uint32_t u = site[i];
@@ -907,7 +841,7 @@ __global__ __launch_bounds__(kU16Threads) void k_hist_site_u16(
   for (; i + 3 * kU16Threads < n16; i += 4 * kU16Threads) {
     uint4 v[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = ld_site<true>(src + i + k * kU16Threads);
+    for (int k = 0; k < 4; ++k) v[k] = ld_nt(src + i + k * kU16Threads);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const uint32_t wd[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
@@ -919,7 +853,7 @@ __global__ __launch_bounds__(kU16Threads) void k_hist_site_u16(
     }
   }
   for (; i < n16; i += kU16Threads) {
-    const uint4 v = ld_site<true>(src + i);
+    const uint4 v = ld_nt(src + i);
     const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -1012,7 +946,6 @@ constexpr int kPctUnroll = 16;
 // workgroup's 256 quantiles are one tile, so it streams contiguous 1 KB runs,
 // site after site -- the lerp off the critical path, and only the f64 add (no
 // contraction) on the in-order dependency chain.
-template <bool NTL>
 __global__ __launch_bounds__(kPctThreads) void k_pct_acc(const uint32_t* __restrict__ vlh,
                                                           int64_t n_sites, int64_t tstride,
                                                           int q_begin, int Q,
@@ -1036,7 +969,7 @@ __global__ __launch_bounds__(kPctThreads) void k_pct_acc(const uint32_t* __restr
   const int64_t last = n_sites - 1;
   auto ld1 = [&](int64_t u) -> uint32_t {
     u = u < last ? u : last;
-    return NTL ? __builtin_nontemporal_load(p + u * ld) : p[u * ld];
+    return p[u * ld];
   };
   uint32_t va[kPctUnroll], vb[kPctUnroll];
 #pragma unroll
@@ -1070,7 +1003,7 @@ void launch_pct_accumulate_range(const uint32_t* vlh, int64_t n_sites, int64_t v
   // the kernel itself runs 5% slower with them, and the +1.7% job throughput
   // measured for this choice (profiles/r1/ab_pct_ntl.txt) is within the
   // run-to-run spread of one build (profiles/r1/noise_same_build.txt).
-  hipLaunchKernelGGL(k_pct_acc<false>, dim3((unsigned)cdiv(q_count, kPctThreads)),
+  hipLaunchKernelGGL(k_pct_acc, dim3((unsigned)cdiv(q_count, kPctThreads)),
                      dim3(kPctThreads), 0, s, vlh, n_sites, vlh_ld * kOsTile, q_begin, q_count,
                      gamma, acc, only_xwide, xthr);
   TMH_HIP(hipGetLastError());

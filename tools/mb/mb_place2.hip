@@ -152,7 +152,7 @@ int main(int argc, char** argv) {
     }
     auto welford = [&](const uint16_t* in, const SiteTab& tab) {
       return time([&] {
-        launch_welford(in, npx, S, 0, rn, mean, m2, lut, 1, part, 8 * npx, 1, wide, 0, 0, -1,
+        launch_welford(in, npx, S, 0, rn, mean, m2, lut, 1, part, 8 * npx, 1, wide, 0, 0,
                        tab);
       });
     };

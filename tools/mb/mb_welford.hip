@@ -83,8 +83,8 @@ template <int MODE>
 __global__ __launch_bounds__(256) void k_wf_abl(const uint16_t* __restrict__ sites, int64_t npx,
                                                 int64_t n_sites, const double* __restrict__ lut,
                                                 double* __restrict__ out) {
-  __shared__ double slut[kWfLut], sinv[kWfLut];
-  fill_wf_tables<1>(lut, slut, sinv, 256);
+  __shared__ double slut[kWfLut];
+  fill_wf_tables(lut, slut, 256);
   __syncthreads();
   uint32_t wc = 0;
   const int64_t ng = npx >> 3;
@@ -94,17 +94,17 @@ __global__ __launch_bounds__(256) void k_wf_abl(const uint16_t* __restrict__ sit
   const int64_t last = n_sites - 1;
   uint4 cur[4], nxt[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) cur[k] = ld_site<true>(src + (k < last ? k : last) * ng);
+  for (int k = 0; k < 4; ++k) cur[k] = ld_nt(src + (k < last ? k : last) * ng);
   double K[8], s1[8], s2[8];
   uint32_t isum = 0;
-  xform8<true, 1>(cur[0], slut, sinv, K, wc, wc);
+  xform8<true>(cur[0], slut, K, wc, wc);
 #pragma unroll
   for (int k = 0; k < 8; ++k) s1[k] = s2[k] = 0.0;
   for (int64_t s = 0; s < n_sites; s += 4) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int64_t t = s + 4 + k;
-      nxt[k] = ld_site<true>(src + (t < last ? t : last) * ng);
+      nxt[k] = ld_nt(src + (t < last ? t : last) * ng);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void k_wf_abl(const uint16_t* __restrict__ sit
 #pragma unroll
           for (int j = 0; j < 8; ++j) x[j] = (double)u[j];
         } else {
-          xform8<true, 1>(v, slut, sinv, x, wc, wc);
+          xform8<true>(v, slut, x, wc, wc);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -151,8 +151,8 @@ template <int G, bool KF, int WPS>
 __global__ __launch_bounds__(256, WPS) void k_wf_var(const uint16_t* __restrict__ sites, int64_t npx,
                                                      int64_t n_sites, const double* __restrict__ lut,
                                                      double* __restrict__ out) {
-  __shared__ double slut[kWfLut], sinv[kWfLut];
-  fill_wf_tables<1>(lut, slut, sinv, 256);
+  __shared__ double slut[kWfLut];
+  fill_wf_tables(lut, slut, 256);
   __syncthreads();
   uint32_t wc = 0;
   const int64_t ng = npx >> 3;
@@ -162,10 +162,10 @@ __global__ __launch_bounds__(256, WPS) void k_wf_var(const uint16_t* __restrict_
   const int64_t last = n_sites - 1;
   uint4 cur[G], nxt[G];
 #pragma unroll
-  for (int k = 0; k < G; ++k) cur[k] = ld_site<true>(src + (k < last ? k : last) * ng);
+  for (int k = 0; k < G; ++k) cur[k] = ld_nt(src + (k < last ? k : last) * ng);
   double K[8], s1[8], s2[8];
   float Kf[8];
-  xform8<true, 1>(cur[0], slut, sinv, K, wc, wc);
+  xform8<true>(cur[0], slut, K, wc, wc);
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     s1[k] = s2[k] = 0.0;
@@ -175,13 +175,13 @@ __global__ __launch_bounds__(256, WPS) void k_wf_var(const uint16_t* __restrict_
 #pragma unroll
     for (int k = 0; k < G; ++k) {
       const int64_t t = s + G + k;
-      nxt[k] = ld_site<true>(src + (t < last ? t : last) * ng);
+      nxt[k] = ld_nt(src + (t < last ? t : last) * ng);
     }
 #pragma unroll
     for (int k = 0; k < G; ++k) {
       if (s + k < n_sites) {
         double x[8];
-        xform8<true, 1>(cur[k], slut, sinv, x, wc, wc);
+        xform8<true>(cur[k], slut, x, wc, wc);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const double d = x[j] - (KF ? (double)Kf[j] : K[j]);
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void k_wf_f32(const uint16_t* __restrict__ sit
   const int64_t last = n_sites - 1;
   uint4 cur[G], nxt[G];
 #pragma unroll
-  for (int k = 0; k < G; ++k) cur[k] = ld_site<true>(src + (k < last ? k : last) * ng);
+  for (int k = 0; k < G; ++k) cur[k] = ld_nt(src + (k < last ? k : last) * ng);
   f2_t Kh[4], Kl[4];
   {
     const uint4 v = cur[0];
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void k_wf_f32(const uint16_t* __restrict__ sit
 #pragma unroll
     for (int k = 0; k < G; ++k) {
       const int64_t t = s + G + k;
-      nxt[k] = ld_site<true>(src + (t < last ? t : last) * ng);
+      nxt[k] = ld_nt(src + (t < last ? t : last) * ng);
     }
 #pragma unroll
     for (int k = 0; k < G; ++k) {
@@ -392,16 +392,12 @@ static int run(int argc, char** argv) {
   var("wf var G2 Kf32 wps6", I2(), B1(), W6());
   var("wf var G4 Kf32 wps5", I4(), B1(), W5());
   var("wf var G1 Kf32 wps6", I1(), B1(), W6());
-  static const char* shapes[9] = {"256 thr, Newton rcp", "256 thr, LDS rcp", "512 thr, Newton rcp",
-                                  "512 thr, LDS rcp", "256 thr, f32 small term", "512 thr, f32 small term"};
-  for (int shape = 0; shape < 9; ++shape)
-    for (int f : {1, 3}) {
-      char nm[80];
-      snprintf(nm, sizeof nm, "welford shape %d (%s) parts %d", shape, shapes[shape], f);
-      time(nm, [&] {
-        launch_welford(in, npx, S, 0, rn, mean, m2, lut, 1, part, 8 * npx, f, nullptr, 0, 0, shape);
-      });
-    }
+  // (the pass's retired shapes -- 256 / 512 threads, f64 reciprocals, 3 and 4
+  // sites per stage -- are in profiles/r2/mb_welford_*_r2za.txt and
+  // profiles/r3/mb_welford_r3h.txt)
+  time("welford production, 3 parts forced", [&] {
+    launch_welford(in, npx, S, 0, rn, mean, m2, lut, 1, part, 8 * npx, 3, nullptr, 0, 0);
+  });
   time("wf f32 G2 blk16", [&] { hipLaunchKernelGGL((k_wf_f32<2, 16>), ag, dim3(256), 0, 0, in, npx, S, lut, mean); });
   time("wf f32 G2 blk32", [&] { hipLaunchKernelGGL((k_wf_f32<2, 32>), ag, dim3(256), 0, 0, in, npx, S, lut, mean); });
   time("wf f32 G4 blk16", [&] { hipLaunchKernelGGL((k_wf_f32<4, 16>), ag, dim3(256), 0, 0, in, npx, S, lut, mean); });
@@ -411,7 +407,7 @@ static int run(int argc, char** argv) {
     time("welford production (parts 1)", [&] {
       launch_welford(in, npx, S, 0, rn, mean, m2, lut, 1, part, 8 * npx, 1, nullptr, 0, 0);
     });
-    time("welford bright form (16,384-entry LUT, 3 parts)", [&] {
+    time("welford bright form (20,472-entry LUT, 3 parts)", [&] {
       launch_welford(in, npx, S, 0, rn, mean, m2, lut, 1, part, 8 * npx, 0, nullptr, 1, 0);
     });
   }
