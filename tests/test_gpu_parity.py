@@ -617,9 +617,10 @@ def test_run_job_auto_mixed_layouts(L, tmp_path, plain):
     assert np.array_equal(mean2, mean) and np.array_equal(vals2, vals)
 
 
-def _fused_job(L, sites, clip=(-1, -1), q=None):
+def _fused_job(L, sites, clip=(-1, -1), q=None, cfg=-1):
     """Split pipeline through the C-ABI: Welford-only update -> finalize ->
-    smooth -> corrector -> fused correct+histogram.  Returns host results."""
+    smooth -> corrector -> fused correct+histogram (cfg: TMH_OPT_FUSED_CONFIG,
+    -1 = the automatic choice).  Returns host results."""
     from tmlibrary_amd import hip
     from tmlibrary_amd.image import ZERO_LOG10
     from tmlibrary_amd.workflow.corilla.quantiles import quantile_table, stats_log10_lut
@@ -632,6 +633,8 @@ def _fused_job(L, sites, clip=(-1, -1), q=None):
     h = C.c_void_p()
     hip.check(L.tmh_stats_create(H, W, Q, hip.ptr(lo), hip.ptr(hi), hip.ptr(gamma),
                                  hip.ptr(lut), 4, hip.TMH_STATS_KEEP_SITE_HIST, C.byref(h)))
+    if cfg != -1:
+        hip.check(L.tmh_stats_set_option(h, hip.TMH_OPT_FUSED_CONFIG, cfg))
     d_in, d_out = Dev(L, sites.nbytes), Dev(L, sites.nbytes)
     d_in.put(sites)
     planes = [Dev(L, npx * 8) for _ in range(5)]
@@ -725,6 +728,52 @@ def test_fused_correct_hist_pipeline(L, kind):
         want = orc.correct_illumination(s, r["smean"], r["sstd"])
         assert_dn(o, want)
     check_order_stats(sites, r["order_stats"])
+
+
+def test_very_wide_keeps_fixups(L):
+    """The fused pass without its histogram (configuration 100, production's
+    very wide form) appends the f64 fixups its units staged in LDS, as every
+    other form does.  A flat patch gives the smoothed std a gain a of about 100
+    at its centre; a ladder of 36 values on it then corrects to values from
+    2**10 to past 2**41, each in an 8-pixel group of its own, all beyond the
+    f32 error bound |o| (K1 a + K2) < 0.998 (common.h), so only the f64
+    refinement brings them within 1 DN of the reference.  The oracle confirms
+    both counts before anything runs on the GPU: they are conditions on the
+    input, not measurements."""
+    from tmlibrary_amd.synth import synth_sites_host
+    sites = np.stack(synth_sites_host(6, 160, 160, seed=41))
+    rng = np.random.default_rng(7)
+    sites[:, 32:128, 32:128] = 1000 + rng.integers(-3, 4, (6, 96, 96))
+    for k, v in enumerate(np.round(1000 * 1.008 ** np.arange(1, 37))):
+        sites[k % 6, 56 + 8 * (k // 6), 56 + 8 * (k % 6)] = v
+    ref = orc.run_illumstats(list(sites))
+    sm, ss = orc.smooth_reflect(ref.mean), orc.smooth_reflect(ref.std)
+    a = np.mean(ss) / ss
+    x = np.where(sites == 0, 1e-10, sites.astype(np.float64))  # image.py: zeros take 1e-10
+    with np.errstate(over="ignore"):
+        o = 10 ** ((np.log10(x) - sm) / ss * np.mean(ss) + np.mean(sm))
+    flagged = np.abs(o) * (6.7e-6 * 1.002 * a + 4.2e-6 * 1.002) >= 0.998
+    assert np.count_nonzero(flagged) >= 30
+    # the value only rounded to f32 and cast as v_cvt_i32_f32 does (saturating)
+    o32 = np.clip(np.trunc(o.astype(np.float32).astype(np.float64)), -2.0 ** 31, 2.0 ** 31 - 1)
+    d = np.abs((o32.astype(np.int64) & 0xFFFF)
+               - orc.cast_float_to_uint_x86(o, np.uint16).astype(np.int64))
+    assert np.count_nonzero(d[flagged] > 1) >= 16  # off by > 1 DN or by a wrap flip
+    hists = [orc.histogram_u16(s) for s in sites]
+    outs = {}
+    for cfg in (100, 3, -1):
+        r = _fused_job(L, sites, cfg=cfg)
+        print("cfg %d ran %d:" % (cfg, r["fused_cfg"]),
+              [dn_report(g, orc.correct_illumination(s, r["smean"], r["sstd"]))
+               for s, g in zip(sites, r["out"])])
+        for s, g in zip(sites, r["out"]):
+            assert_dn(g, orc.correct_illumination(s, r["smean"], r["sstd"]))
+        for sh, want in zip(r["site_hist"], hists):
+            assert np.array_equal(sh.astype(np.uint64), want)
+        assert np.array_equal(r["hist"], sum(hists))
+        assert np.array_equal(r["acc"], ref.percentile_sums)
+        outs[cfg] = r["out"]
+    assert np.array_equal(outs[100], outs[3])
 
 
 def test_bright_welford_table_edges(L):

@@ -96,9 +96,9 @@ static void corrector_init(tmh_corrector* c, const double* d_mean, const double*
 
 // The refinement list of one correct launch over n_sites sites on stream s:
 // capacity for 1/1024 of the launch's pixels (an overflow makes the fixup
-// recompute every pixel in f64: slow but exact), count reset on s.  One
-// launch at a time per corrector (the list is reused).
-FixList corrector_fixlist(tmh_corrector* c, int64_t n_sites, hipStream_t s, bool reset) {
+// recompute every pixel in f64: slow but exact).  One launch at a time per
+// corrector (the list is reused).  The caller zeroes the count ...
+FixList corrector_fixlist(tmh_corrector* c, int64_t n_sites) {
   TMH_CHECK(n_sites < ((int64_t)1 << 24), TMH_EINVAL, "at most 2^24 - 1 sites per correct call");
   const int64_t want = std::min<int64_t>(std::max<int64_t>((int64_t)1 << 20, n_sites * c->npx / 1024),
                                          (int64_t)1 << 30);
@@ -106,8 +106,14 @@ FixList corrector_fixlist(tmh_corrector* c, int64_t n_sites, hipStream_t s, bool
     TMH_HIP(hipDeviceSynchronize());  // the list may be in use on any stream
     c->fix_e.alloc((size_t)want);
   }
-  if (reset) TMH_HIP(hipMemsetAsync(c->fix_n.p, 0, sizeof(unsigned int), s));
   return FixList{c->fix_e.p, c->fix_n.p, (unsigned int)c->fix_e.n};
+}
+
+// ... or has it reset here, on s
+FixList corrector_fixlist(tmh_corrector* c, int64_t n_sites, hipStream_t s) {
+  const FixList fl = corrector_fixlist(c, n_sites);
+  TMH_HIP(hipMemsetAsync(fl.n, 0, sizeof(unsigned int), s));
+  return fl;
 }
 
 void check_clip(int lo, int hi, int maxv) {

@@ -4,8 +4,9 @@
 namespace tmh {
 
 // One job's fused pass (correct + per-site histograms, then the histogram
-// tail), in three steps so several jobs can share the launch in between
-// (tmh_correct_u16_hist_multi_device): fused_prepare -> launch -> fused_finish.
+// tail), in steps so several jobs can share the launches in between
+// (correct_hist_multi): fused_prepare -> resets, launch, fixups -> fused_post
+// -> the tail (fused_tail, or every job's at once and fused_tail_end).
 struct FusedPass {
   tmh_corrector* c;
   tmh_stats* h;
@@ -56,22 +57,13 @@ static bool fused_begin(tmh_corrector* c, tmh_stats* h, hipStream_t s) {
   return cross;
 }
 
-// buffers, rare lists, fixup list and the configuration of one job's pass
-// (batched: the caller zeroes the fixup counter with its other jobs')
-static void fused_prepare(FusedPass& p, bool batched = false) {
-  tmh_stats* h = p.h;
-  tmh_corrector* c = p.c;
-  const int64_t n_sites = p.n;
-  hipStream_t s = p.s;
-  // rare lists (RareList, common.h) for the packed configuration
-  if (h->fused_cfg == kFusedAuto) stats_probe(h, p.in, n_sites, p.tab, s);
-  const bool rl_on = probe_fused_cfg(h) == kFusedWide;
-  const unsigned int rl_cap =
-      (unsigned int)std::min<int64_t>(65536, std::max<int64_t>(1024, h->npx / 64));
-  const bool grow = (size_t)n_sites * kBins > h->hist_full.n || (size_t)n_sites > h->zeros.n ||
-                    (size_t)n_sites > h->hist_rmask.n ||
-                    (rl_on && ((size_t)n_sites * rl_cap > h->rare_v.n ||
-                               (size_t)n_sites > h->rare_n.n)) ||
+// The per-site buffers of a pass over n_sites sites and where its order
+// statistics go (vlh, of a buffer with room for ld sites).  Growing frees
+// memory earlier launches may still use: the streams are drained first (more:
+// the caller has buffers of its own to grow after this).
+static void pass_buffers(tmh_stats* h, int64_t n_sites, hipStream_t s, bool more, uint32_t*& vlh,
+                         int64_t& ld) {
+  const bool grow = more || (size_t)n_sites > h->zeros.n ||
                     ((h->flags & 2u) && (size_t)n_sites * kBins > h->site_hist.n) ||
                     (!(h->flags & TMH_STATS_DEFERRED_PCT) && os_words(h, n_sites) > h->vlh.n);
   if (grow) {
@@ -79,6 +71,35 @@ static void fused_prepare(FusedPass& p, bool batched = false) {
     TMH_HIP(hipStreamSynchronize(hstream(h)));
     TMH_HIP(hipStreamSynchronize(h->side));
   }
+  h->zeros.ensure((size_t)n_sites);
+  if (h->flags & 2u) h->site_hist.ensure((size_t)n_sites * kBins);
+  if (h->flags & TMH_STATS_DEFERRED_PCT) {
+    stats_grow_deferred(h, n_sites);
+    vlh = h->vlh.p + (size_t)h->n_deferred * kOsTile;
+    ld = h->vlh_cap;
+  } else {
+    h->vlh.ensure(os_words(h, n_sites));
+    vlh = h->vlh.p;
+    ld = n_sites;
+  }
+  h->vlh_ld = ld;
+}
+
+// buffers, rare lists, fixup list and the configuration of one job's pass
+// (the caller zeroes the fixup counter and the unit queues with its other jobs')
+static void fused_prepare(FusedPass& p) {
+  tmh_stats* h = p.h;
+  const int64_t n_sites = p.n;
+  hipStream_t s = p.s;
+  // rare lists (RareList, common.h) for the packed configuration
+  if (h->fused_cfg == kFusedAuto) stats_probe(h, p.in, n_sites, p.tab, s);
+  const bool rl_on = probe_fused_cfg(h) == kFusedWide;
+  const unsigned int rl_cap =
+      (unsigned int)std::min<int64_t>(65536, std::max<int64_t>(1024, h->npx / 64));
+  const bool more = (size_t)n_sites * kBins > h->hist_full.n || (size_t)n_sites > h->hist_rmask.n ||
+                    (rl_on && ((size_t)n_sites * rl_cap > h->rare_v.n ||
+                               (size_t)n_sites > h->rare_n.n));
+  pass_buffers(h, n_sites, s, more, p.vlh, p.ld);
   if ((size_t)n_sites * kBins > h->hist_full.n) h->hist_full.alloc((size_t)n_sites * kBins, true);
   if ((size_t)n_sites > h->hist_rmask.n) h->hist_rmask.alloc((size_t)n_sites, true);
   p.rl = RareList{};
@@ -88,18 +109,6 @@ static void fused_prepare(FusedPass& p, bool batched = false) {
     TMH_HIP(hipMemsetAsync(h->rare_n.p, 0, (size_t)n_sites * sizeof(unsigned int), s));
     p.rl = RareList{h->rare_v.p, h->rare_n.p, rl_cap};
   }
-  h->zeros.ensure((size_t)n_sites);
-  if (h->flags & 2u) h->site_hist.ensure((size_t)n_sites * kBins);
-  if (h->flags & TMH_STATS_DEFERRED_PCT) {
-    stats_grow_deferred(h, n_sites);
-    p.vlh = h->vlh.p + (size_t)h->n_deferred * kOsTile;
-    p.ld = h->vlh_cap;
-  } else {
-    h->vlh.ensure(os_words(h, n_sites));
-    p.vlh = h->vlh.p;
-    p.ld = n_sites;
-  }
-  h->vlh_ld = p.ld;
   // the histogram slab and round masks are zero-maintained: the fused pass
   // fills them and k_hist_finalize resets what it read; if anything fails in
   // between, tmh_stats_reset clears them (hist_dirty)
@@ -108,30 +117,23 @@ static void fused_prepare(FusedPass& p, bool batched = false) {
   // one configuration, chosen on the host from the job's site probe (probed
   // at the Welford launch, or above for a job whose Welford pass did not)
   p.cfg = probe_fused_cfg(h);
-  p.fl = corrector_fixlist(c, n_sites, s, !batched);
+  p.fl = corrector_fixlist(p.c, n_sites);
 }
 
-// what follows the job's fused launch up to its histogram tail: rare lists,
-// f64 fixups and the very wide configuration's histograms.  fixed: the caller
-// launched the fixups (and the wide counters' reset) for several jobs at once.
-static void fused_post(FusedPass& p, bool fixed) {
+// what follows the job's fused launch and fixups up to its histogram tail:
+// rare lists and the very wide configuration's histograms
+static void fused_post(FusedPass& p) {
   tmh_stats* h = p.h;
-  tmh_corrector* c = p.c;
   const int64_t n_sites = p.n;
   hipStream_t s = p.s;
   if (p.cfg == kFusedWide) launch_rare_count(p.rl, h->hist_full.p, n_sites, s);
-  if (!fixed)
-    launch_fix_correct(p.in, p.out, 2, c->npx, n_sites, p.fl, c->coef64.p, c->rc.p,
-                       c->log_transform, p.clip_lo, p.clip_hi, s, p.tab);
   if (p.cfg == kFusedNoHist)  // the histograms from one more read of the sites
     launch_hist_site_u16(p.in, h->npx, n_sites, h->hist_full.p, h->qp, p.vlh, p.ld, h->pooled.p,
                          h->pooled_parts.p, h->zeros.p, p.sh, s, p.tab);
   // the Welford pass's diagnostic wide counts restart with the next batch
-  // (reset here on s, before any later Welford launch on the handle)
-  if (h->pending - n_sites == 0) {
-    if (!fixed) TMH_HIP(hipMemsetAsync(h->wide.p, 0, 16, s));
-    h->wide_sites = 0;
-  }
+  // (the fixup launch reset them on s, before any later Welford launch on
+  // the handle)
+  if (h->pending - n_sites == 0) h->wide_sites = 0;
 }
 
 // The histogram tail (order statistics, percentile sums) reads only the
@@ -188,88 +190,49 @@ static void fused_tail(FusedPass& p) {
   fused_tail_end(p, ts);
 }
 
-static void fused_finish(FusedPass& p) {
-  fused_post(p, false);
-  fused_tail(p);
-}
-
-static void correct_hist_dev(tmh_corrector* c, tmh_stats* h, const uint16_t* dev_in,
-                             uint16_t* dev_out, int64_t n_sites, int clip_lo, int clip_hi,
-                             void* stream, const SiteTab& tab) {
-  {
-    fused_check(c, h, n_sites);
-    check_clip(clip_lo, clip_hi, 65535);
-    if (n_sites == 0) return;
-    hipStream_t s = pick(c->stream, stream);
-    const bool vec = fused_vec(c, h, dev_in, dev_out, tab);
-    const bool cross = fused_begin(c, h, s);
-    if (vec) {
-      FusedPass p{c, h, dev_in, dev_out, n_sites, tab, s, cross, clip_lo, clip_hi};
-      fused_prepare(p);
-      launch_correct_hist(dev_in, dev_out, c->npx, n_sites, c->coef2.p, c->mconst2.p, p.fl,
-                          c->log_transform, clip_lo, clip_hi, h->hist_full.p, h->hist_rmask.p,
-                          c->queues.p, c->n_wg, p.cfg, c->bands, s, tab, p.rl);
-      fused_finish(p);
-      return;
-    }
-    const int64_t chunk = 4096;  // odd shapes: correct and histogram in two passes
-    for (int64_t c0 = 0; c0 < n_sites; c0 += chunk) {
-      const int64_t nc = std::min(chunk, n_sites - c0);
-      const uint16_t* din = dev_in + c0 * h->npx;
-      uint16_t* dout = dev_out + c0 * h->npx;
-      // per-site buffers (growing frees memory earlier launches may still use)
-      const bool grow = (size_t)nc > h->zeros.n ||
-                        ((h->flags & 2u) && (size_t)nc * kBins > h->site_hist.n) ||
-                        (!(h->flags & TMH_STATS_DEFERRED_PCT) && os_words(h, nc) > h->vlh.n);
-      if (grow) {
-        TMH_HIP(hipStreamSynchronize(s));
-        TMH_HIP(hipStreamSynchronize(hstream(h)));
-        TMH_HIP(hipStreamSynchronize(h->side));
-      }
-      h->zeros.ensure((size_t)nc);
-      if (h->flags & 2u) h->site_hist.ensure((size_t)nc * kBins);
-      uint32_t* vlh;
-      int64_t ld;
-      if (h->flags & TMH_STATS_DEFERRED_PCT) {
-        stats_grow_deferred(h, nc);
-        vlh = h->vlh.p + (size_t)h->n_deferred * kOsTile;
-        ld = h->vlh_cap;
-      } else {
-        h->vlh.ensure(os_words(h, nc));
-        vlh = h->vlh.p;
-        ld = nc;
-      }
-      h->vlh_ld = ld;
-      stats_reserve_sites(h, nc);
-      const FixList fl = corrector_fixlist(c, nc, s);
-      corrector_forms(c, s);
-      launch_correct_u16(din, dout, c->npx, nc, c->coef.p, c->lut.p, c->mconst.p, fl,
-                         c->log_transform, clip_lo, clip_hi, s);
-      launch_fix_correct(din, dout, 2, c->npx, nc, fl, c->coef64.p, c->rc.p, c->log_transform,
-                         clip_lo, clip_hi, s);
-      launch_hist_scatter(din, h->npx, nc, h->hist_hi.p, h->qp, vlh, ld, h->pooled.p, h->zeros.p,
-                          (h->flags & 2u) ? h->site_hist.p : nullptr, s);
-      if (h->flags & TMH_STATS_DEFERRED_PCT)
-        h->n_deferred += nc;
-      else
-        launch_pct_accumulate(vlh, nc, ld, h->Q, h->gamma.p, h->acc.p, s);
-      h->last_batch = nc;
-      h->pending -= nc;
-    }
-    if (h->pending == 0 && h->wide_sites) {
-      TMH_HIP(hipMemsetAsync(h->wide.p, 0, 16, s));
-      h->wide_sites = 0;
-    }
-    if (cross) defer_join(h, s);
+// Odd shapes (fused_vec): correct and histogram in two passes
+static void correct_hist_two_pass(tmh_corrector* c, tmh_stats* h, const uint16_t* dev_in,
+                                  uint16_t* dev_out, int64_t n_sites, int clip_lo, int clip_hi,
+                                  hipStream_t s) {
+  const bool cross = fused_begin(c, h, s);
+  const int64_t chunk = 4096;
+  for (int64_t c0 = 0; c0 < n_sites; c0 += chunk) {
+    const int64_t nc = std::min(chunk, n_sites - c0);
+    const uint16_t* din = dev_in + c0 * h->npx;
+    uint16_t* dout = dev_out + c0 * h->npx;
+    uint32_t* vlh;
+    int64_t ld;
+    pass_buffers(h, nc, s, false, vlh, ld);
+    stats_reserve_sites(h, nc);
+    const FixList fl = corrector_fixlist(c, nc, s);
+    corrector_forms(c, s);
+    launch_correct_u16(din, dout, c->npx, nc, c->coef.p, c->lut.p, c->mconst.p, fl,
+                       c->log_transform, clip_lo, clip_hi, s);
+    launch_fix_correct(din, dout, 2, c->npx, nc, fl, c->coef64.p, c->rc.p, c->log_transform,
+                       clip_lo, clip_hi, s);
+    launch_hist_scatter(din, h->npx, nc, h->hist_hi.p, h->qp, vlh, ld, h->pooled.p, h->zeros.p,
+                        (h->flags & 2u) ? h->site_hist.p : nullptr, s);
+    if (h->flags & TMH_STATS_DEFERRED_PCT)
+      h->n_deferred += nc;
+    else
+      launch_pct_accumulate(vlh, nc, ld, h->Q, h->gamma.p, h->acc.p, s);
+    h->last_batch = nc;
+    h->pending -= nc;
   }
+  if (h->pending == 0 && h->wide_sites) {
+    TMH_HIP(hipMemsetAsync(h->wide.p, 0, 16, s));
+    h->wide_sites = 0;
+  }
+  if (cross) defer_join(h, s);
 }
 
-// Several jobs' fused passes in ONE launch (a rank's channels): a short job's
-// launch ends with most workgroups idle for a unit's time and starts with the
-// pipeline filling; one sweep over every job's units pays that once.  Jobs
-// whose configuration differs from the first's, or that need the two-pass
-// path, run their own passes on the same stream; results are the per-job
-// calls' in every case.
+// One or several jobs' fused passes in ONE launch (a rank's channels): a short
+// job's launch ends with most workgroups idle for a unit's time and starts
+// with the pipeline filling; one sweep over every job's units pays that once.
+// A job whose configuration differs from the first's gets a launch of its
+// own, and a call with a job that needs the two-pass path runs its jobs one
+// by one, all on the same stream; results are the per-job calls' in every
+// case.
 static void correct_hist_multi(tmh_corrector* const* cs, tmh_stats* const* hs, int n_jobs,
                                const uint16_t* const* ins, uint16_t* const* outs,
                                const SiteTab* tabs, const int64_t* n_sites, int clip_lo,
@@ -287,14 +250,21 @@ static void correct_hist_multi(tmh_corrector* const* cs, tmh_stats* const* hs, i
                 "each job needs its own corrector and statistics handle");
   }
   hipStream_t s = pick(cs[0]->stream, stream);
-  bool all_vec = true;
-  for (int j = 0; j < n_jobs; ++j)
-    all_vec = all_vec && fused_vec(cs[j], hs[j], ins ? ins[j] : nullptr,
-                                   outs ? outs[j] : nullptr, tabs[j]);
+  bool vec[kMaxJobs], all_vec = true;
+  for (int j = 0; j < n_jobs; ++j) {
+    vec[j] = fused_vec(cs[j], hs[j], ins ? ins[j] : nullptr, outs ? outs[j] : nullptr, tabs[j]);
+    all_vec = all_vec && vec[j];
+  }
   if (!all_vec) {
-    for (int j = 0; j < n_jobs; ++j)
-      correct_hist_dev(cs[j], hs[j], ins ? ins[j] : nullptr, outs ? outs[j] : nullptr, n_sites[j],
-                       clip_lo, clip_hi, s, tabs[j]);
+    for (int j = 0; j < n_jobs; ++j) {
+      if (n_sites[j] == 0) continue;
+      hipStream_t sj = pick(cs[j]->stream, s);
+      if (vec[j])
+        correct_hist_multi(cs + j, hs + j, 1, ins + j, outs + j, tabs + j, n_sites + j, clip_lo,
+                           clip_hi, sj);
+      else
+        correct_hist_two_pass(cs[j], hs[j], ins[j], outs[j], n_sites[j], clip_lo, clip_hi, sj);
+    }
     return;
   }
   FusedPass p[kMaxJobs];
@@ -304,41 +274,40 @@ static void correct_hist_multi(tmh_corrector* const* cs, tmh_stats* const* hs, i
     const bool cross = fused_begin(cs[j], hs[j], s);
     p[np] = FusedPass{cs[j], hs[j], ins ? ins[j] : nullptr, outs ? outs[j] : nullptr, n_sites[j],
                       tabs[j], s, cross, clip_lo, clip_hi};
-    fused_prepare(p[np], true);
+    fused_prepare(p[np]);
     ++np;
   }
   if (np == 0) return;
-  // every job's fixup counter, and the unit queues of the jobs sharing the
-  // first job's launch, zeroed by one kernel (a fill per array cost ~10 us
-  // each on the pass stream, 8 of them ahead of a four-job launch)
+  // every job's fixup counter and unit queues, zeroed by one kernel (a fill
+  // per array cost ~10 us each on the pass stream, 8 of them ahead of a
+  // four-job launch)
   ZeroList32 Z;
   for (int j = 0; j < np; ++j) {
     Z.add(p[j].c->fix_n.p, 1);
-    if (p[j].cfg == p[0].cfg) Z.add(p[j].c->queues.p, kFusedQueueInts);
+    Z.add(p[j].c->queues.p, kFusedQueueInts);
   }
   launch_zero_u32(Z, s);
+  // the jobs of the first job's configuration in one launch, whose unit
+  // counters are the first job's queues[0..8); every job's round-mask union
+  // is its own corrector's queues + 8
+  tmh_corrector* c0 = p[0].c;
   FusedJobs J{};
   for (int j = 0; j < np; ++j) {
-    if (p[j].cfg != p[0].cfg) {  // its own launch
-      tmh_corrector* c = p[j].c;
-      launch_correct_hist(p[j].in, p[j].out, c->npx, p[j].n, c->coef2.p, c->mconst2.p, p[j].fl,
-                          c->log_transform, clip_lo, clip_hi, p[j].h->hist_full.p,
-                          p[j].h->hist_rmask.p, c->queues.p, c->n_wg, p[j].cfg, c->bands, s,
-                          p[j].tab, p[j].rl);
+    tmh_corrector* c = p[j].c;
+    const FusedJob job{p[j].in, p[j].out, p[j].n, reinterpret_cast<const float4*>(c->coef2.p),
+                       c->mconst2.p, p[j].fl, p[j].h->hist_full.p, p[j].h->hist_rmask.p,
+                       reinterpret_cast<unsigned long long*>(c->queues.p + 8), p[j].tab, p[j].rl};
+    if (p[j].cfg == p[0].cfg) {
+      J.j[J.n++] = job;
       continue;
     }
-    tmh_corrector* c = p[j].c;
-    // the launch's unit counters are the first job's queues[0..8); every
-    // job's round-mask union is its own corrector's queues + 8 (zeroed above)
-    J.j[J.n++] = FusedJob{p[j].in, p[j].out, p[j].n,
-                          reinterpret_cast<const float4*>(c->coef2.p), c->mconst2.p, p[j].fl,
-                          p[j].h->hist_full.p, p[j].h->hist_rmask.p,
-                          reinterpret_cast<unsigned long long*>(c->queues.p + 8), p[j].tab,
-                          p[j].rl};
+    FusedJobs own{};  // another configuration: its own launch
+    own.j[own.n++] = job;
+    launch_correct_hist(own, c->npx, c->log_transform, clip_lo, clip_hi, c->queues.p, c->n_wg,
+                        p[j].cfg, c->bands, s);
   }
-  tmh_corrector* c0 = p[0].c;
-  launch_correct_hist_jobs(J, c0->npx, c0->log_transform, clip_lo, clip_hi, c0->queues.p, c0->n_wg,
-                           p[0].cfg, c0->bands, s);
+  launch_correct_hist(J, c0->npx, c0->log_transform, clip_lo, clip_hi, c0->queues.p, c0->n_wg,
+                      p[0].cfg, c0->bands, s);
   // every job's fixups (and Welford wide-counter reset) in one launch
   FixJobs F{};
   for (int j = 0; j < np; ++j) {
@@ -347,7 +316,7 @@ static void correct_hist_multi(tmh_corrector* const* cs, tmh_stats* const* hs, i
                         p[j].h->pending - p[j].n == 0 ? p[j].h->wide.p : nullptr};
   }
   launch_fix_correct_jobs(F, c0->npx, c0->log_transform, clip_lo, clip_hi, s);
-  for (int j = 0; j < np; ++j) fused_post(p[j], true);
+  for (int j = 0; j < np; ++j) fused_post(p[j]);
   // every job's histogram tail (column sums, order statistics) in two
   // launches on one stream: the first job's tail stream when the jobs run
   // off their handles' streams, else s
@@ -364,6 +333,16 @@ static void correct_hist_multi(tmh_corrector* const* cs, tmh_stats* const* hs, i
       T.j[T.n++] = tail_job(p[j]);
   launch_hist_finalize_jobs(T, ts);
   for (int j = 0; j < np; ++j) fused_tail_end(p[j], ts);
+}
+
+// One job (the single-job entry points): the several-jobs path with one job
+static void correct_hist_dev(tmh_corrector* c, tmh_stats* h, const uint16_t* dev_in,
+                             uint16_t* dev_out, int64_t n_sites, int clip_lo, int clip_hi,
+                             void* stream, const SiteTab& tab) {
+  fused_check(c, h, n_sites);
+  check_clip(clip_lo, clip_hi, 65535);
+  if (n_sites == 0) return;
+  correct_hist_multi(&c, &h, 1, &dev_in, &dev_out, &tab, &n_sites, clip_lo, clip_hi, stream);
 }
 
 }  // namespace tmh

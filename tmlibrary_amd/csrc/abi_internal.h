@@ -309,7 +309,8 @@ void stats_probe(tmh_stats* h, const uint16_t* d, int64_t ns, const SiteTab& tab
 int probe_fused_cfg(const tmh_stats* h);
 SiteTab blocked_tab(const uint16_t* const* dev_in_blocks, uint16_t* const* dev_out_blocks,
                     int block_shift, int64_t npx);
-FixList corrector_fixlist(tmh_corrector* c, int64_t n_sites, hipStream_t s, bool reset = true);
+FixList corrector_fixlist(tmh_corrector* c, int64_t n_sites);  // the caller zeroes the count
+FixList corrector_fixlist(tmh_corrector* c, int64_t n_sites, hipStream_t s);  // reset on s
 void corrector_forms(tmh_corrector* c, hipStream_t s);
 void check_clip(int lo, int hi, int maxv);
 

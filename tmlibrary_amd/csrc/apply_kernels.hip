@@ -309,7 +309,7 @@ __device__ __forceinline__ void smooth2d_blk_body(const double* __restrict__ in,
     return i < 0 ? -1 - i : (i >= n ? 2 * n - 1 - i : i);
   };
   const double* __restrict__ col = in + refl(x0 - R + tid, W);
-  // the taps are symmetric bit for bit (abi.hip gaussian_taps writes w[R + i]
+  // the taps are symmetric bit for bit (abi_apply.hip gaussian_taps writes w[R + i]
   // and w[R - i] from one value): 21 scalar registers' worth, not 41
   double wk[K];
 #pragma unroll
@@ -663,7 +663,7 @@ __device__ __forceinline__ void fix_correct_body(const T* __restrict__ in, T* __
     fix_entry(fl, all, i, npx, s, p0, mask);
     const T* si = in + s * npx;
     T* so = out + s * npx;
-    if (tab.in) {  // blocked layout (u16 launches only)
+    if (tab.in) {  // blocked layout (the fused pass's jobs only)
       const int64_t b = site_block(tab, s), o = site_in_block(tab, s) * npx;
       si = reinterpret_cast<const T*>(tab.in[b]) + o;
       so = reinterpret_cast<T*>(tab.out[b]) + o;
@@ -689,8 +689,8 @@ __global__ __launch_bounds__(256) void k_fix_correct(const T* __restrict__ in, T
                                                      int64_t npx, int64_t n_sites, FixList fl,
                                                      const double2* __restrict__ c64,
                                                      const RefineConst* __restrict__ rc,
-                                                     int clip_lo, int clip_hi, const SiteTab tab) {
-  fix_correct_body<LOG, T, BITS>(in, out, npx, n_sites, fl, c64, rc, clip_lo, clip_hi, tab);
+                                                     int clip_lo, int clip_hi) {
+  fix_correct_body<LOG, T, BITS>(in, out, npx, n_sites, fl, c64, rc, clip_lo, clip_hi, SiteTab{});
 }
 
 // Several jobs' fixups in one launch (blockIdx.y = job, uint16 sites), each
@@ -717,29 +717,27 @@ void launch_fix_correct_jobs(const FixJobs& J, int64_t npx, int log_transform, i
 
 void launch_fix_correct(const void* in, void* out, int elem_bytes, int64_t npx, int64_t n_sites,
                         const FixList& fl, const double2* coef64, const RefineConst* rc,
-                        int log_transform, int clip_lo, int clip_hi, hipStream_t s,
-                        const SiteTab& tab) {
+                        int log_transform, int clip_lo, int clip_hi, hipStream_t s) {
   if (n_sites <= 0) return;
   const dim3 grid(512), block(256);
-  TMH_CHECK(!tab.in || elem_bytes == 2, TMH_EINVAL, "blocked layouts are uint16 only");
   if (elem_bytes == 2) {
     auto i16 = static_cast<const uint16_t*>(in);
     auto o16 = static_cast<uint16_t*>(out);
     if (log_transform)
       hipLaunchKernelGGL((k_fix_correct<true, uint16_t, 16>), grid, block, 0, s, i16, o16, npx,
-                         n_sites, fl, coef64, rc, clip_lo, clip_hi, tab);
+                         n_sites, fl, coef64, rc, clip_lo, clip_hi);
     else
       hipLaunchKernelGGL((k_fix_correct<false, uint16_t, 16>), grid, block, 0, s, i16, o16, npx,
-                         n_sites, fl, coef64, rc, clip_lo, clip_hi, tab);
+                         n_sites, fl, coef64, rc, clip_lo, clip_hi);
   } else {
     auto i8 = static_cast<const uint8_t*>(in);
     auto o8 = static_cast<uint8_t*>(out);
     if (log_transform)
       hipLaunchKernelGGL((k_fix_correct<true, uint8_t, 8>), grid, block, 0, s, i8, o8, npx, n_sites,
-                         fl, coef64, rc, clip_lo, clip_hi, tab);
+                         fl, coef64, rc, clip_lo, clip_hi);
     else
       hipLaunchKernelGGL((k_fix_correct<false, uint8_t, 8>), grid, block, 0, s, i8, o8, npx,
-                         n_sites, fl, coef64, rc, clip_lo, clip_hi, tab);
+                         n_sites, fl, coef64, rc, clip_lo, clip_hi);
   }
   TMH_HIP(hipGetLastError());
 }

@@ -257,22 +257,22 @@ struct ZeroList {
   }
 };
 void launch_zero_u64(const ZeroList& z, hipStream_t s);
-// Small u32 arrays zeroed in one launch (a multi-job corrected pass's
-// per-job fixup counters and unit queues: one kernel, not a fill per array)
+constexpr int kMaxJobs = 8;          // jobs (a rank's channels) of one multi-job launch
+// Small u32 arrays zeroed in one launch (a fused pass's per-job fixup
+// counters and unit queues: one kernel, not a fill per array)
 struct ZeroList32 {
-  unsigned int* p[16];
-  int count[16];  // u32 elements
+  static constexpr int kCap = 2 * kMaxJobs;  // two arrays per job
+  unsigned int* p[kCap];
+  int count[kCap];  // u32 elements
   int n = 0;
   void add(void* ptr, int elems) {
-    TMH_CHECK(n < 16, TMH_EINVAL, "zero list is full");
+    TMH_CHECK(n < kCap, TMH_EINVAL, "zero list is full");
     p[n] = static_cast<unsigned int*>(ptr);
     count[n++] = elems;
   }
 };
 void launch_zero_u32(const ZeroList32& z, hipStream_t s);
 
-constexpr int kMaxJobs = 8;          // jobs (a rank's channels) of one multi-job launch
-static_assert(2 * kMaxJobs <= 16, "ZeroList32 holds two arrays per job of a multi-job launch");
 // Fused jobs' histogram tails: per job the pooled histogram (a column sum of
 // the sites' histograms over the rounds the masks name) and every site's
 // order statistics, in two launches for all the jobs
@@ -346,12 +346,13 @@ void launch_coeffs_jobs(const CoefJobs& J, int n_jobs, int H, int W, bool partia
 void launch_coeffs_forms(const double2* coef64, const double* sums, int64_t npx, int log_transform,
                          float4* coef, float2* coef_lin, hipStream_t s);
 // Refinement of the pixels a correct launch flagged (fl), written into out
-// (u16 or u8 of in's type; clip as the launch); launched on the same stream.
+// (u16 or u8 of in's type, contiguous sites; clip as the launch); launched on
+// the same stream.
 void launch_fix_correct(const void* in, void* out, int elem_bytes, int64_t npx, int64_t n_sites,
                         const FixList& fl, const double2* coef64, const RefineConst* rc,
-                        int log_transform, int clip_lo, int clip_hi, hipStream_t s,
-                        const SiteTab& tab = SiteTab{});
-// Several uint16 jobs' fixups in one launch (the multi-job fused pass)
+                        int log_transform, int clip_lo, int clip_hi, hipStream_t s);
+// The fused pass's fixups: one or several uint16 jobs (contiguous or blocked)
+// in one launch
 struct FixJob {
   const uint16_t* in;
   uint16_t* out;
@@ -402,20 +403,12 @@ constexpr double kBrightFrac = 0.10;
 // the fused pass without its histogram (very wide sites: k_hist_site_u16
 // builds the histograms)
 constexpr int kFusedNoHist = 100;
-// cfg: 0 .. kFusedConfigs - 1 or kFusedNoHist -- exactly one launch; bands:
-// pixel bands of the unit sweep (0: the configuration's, more for a short
-// launch -- fused_kernels.hip fused_bands)
-void launch_correct_hist(const uint16_t* in, uint16_t* out, int64_t npx, int64_t n_sites,
-                         const float2* coef2, const float4* mconst2, const FixList& fl,
-                         int log_transform, int clip_lo, int clip_hi, uint32_t* hist,
-                         unsigned long long* rmask, int* queues, int n_wg, int cfg, int bands,
-                         hipStream_t s, const SiteTab& tab = SiteTab{},
-                         const RareList& rl = RareList{});
-// One fused pass over several jobs (a rank's channels, same image size,
-// configuration and transform): job j's units follow job j-1's in one sweep,
-// each unit with its own job's sites, coefficients, histograms, round masks
-// and fixup list.  uni: the job's round-mask union (its corrector's
-// queues + 8, zeroed by the caller); queues: the launch's unit counters.
+// One fused pass over one or several jobs (a rank's channels, same image
+// size, configuration and transform): job j's units follow job j-1's in one
+// sweep, each unit with its own job's sites, coefficients, histograms, round
+// masks and fixup list.  uni: the job's round-mask union (its corrector's
+// queues + 8); queues: the launch's kFusedQueueInts unit counters; the caller
+// zeroes both on the launch's stream.
 struct FusedJob {
   const uint16_t* in;
   uint16_t* out;
@@ -433,9 +426,11 @@ struct FusedJobs {
   FusedJob j[kMaxJobs];
   int n;
 };
-void launch_correct_hist_jobs(const FusedJobs& J, int64_t npx, int log_transform, int clip_lo,
-                              int clip_hi, int* queues, int n_wg, int cfg, int bands,
-                              hipStream_t s);
+// cfg: 0 .. kFusedConfigs - 1 or kFusedNoHist -- exactly one launch; bands:
+// pixel bands of the unit sweep (0: the configuration's, more for a short
+// launch -- fused_kernels.hip fused_bands)
+void launch_correct_hist(const FusedJobs& J, int64_t npx, int log_transform, int clip_lo,
+                         int clip_hi, int* queues, int n_wg, int cfg, int bands, hipStream_t s);
 // after launch_correct_hist with a RareList: each site's list into its
 // histogram (hist + s * kBins), on the same stream
 void launch_rare_count(const RareList& rl, uint32_t* hist, int64_t n_sites, hipStream_t s);

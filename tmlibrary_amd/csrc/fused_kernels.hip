@@ -40,14 +40,8 @@ namespace tmh {
 
 constexpr int kFusedBands = 16;  // pixel bands of the unit sweep
 // cache policy bits of the site loads and corrected stores (2: streamed,
-// non-temporal); overridable at build time for A/B builds
-#ifndef TMH_FUSED_LOAD_AUX
-#define TMH_FUSED_LOAD_AUX 2
-#endif
-#ifndef TMH_FUSED_STORE_AUX
-#define TMH_FUSED_STORE_AUX 2
-#endif
-constexpr int kFusedLoadAux = TMH_FUSED_LOAD_AUX, kFusedStoreAux = TMH_FUSED_STORE_AUX;
+// non-temporal)
+constexpr int kFusedLoadAux = 2, kFusedStoreAux = 2;
 
 // A pointer every lane holds the same value of, moved to scalar registers: a
 // buffer resource built from a pointer loaded with a vector load (a block
@@ -177,9 +171,10 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
   return v;
 }
 
-// ABL: development ablations (tools/mb), 0 in production: 1 = no histogram,
-// 2 = constant coefficients, 8 = no flush, 32 = no arithmetic, 64 = values
-// beyond the slices not staged (the rare path's loop skipped).
+// ABL: 0, or bit 1 = no histogram (production's very wide form, kFusedNoHist:
+// the pixel loop's counting and the slice work at the end of a unit are left
+// out, nothing else), bit 32 = no arithmetic (tools/mb only: with bit 1 the
+// copy-rate instrument abl33).
 // NT threads per workgroup, LB LDS bins per workgroup (split into SPU slices
 // of BINS counters plus one overflow counter each: a pixel >= BINS adds to the
 // overflow counter -- never read -- and to its global bin, so the common path
@@ -327,12 +322,10 @@ __global__ __launch_bounds__(NT, (LB * 4 > 80 * 1024 && NT <= 512) ? 2 : 4) void
                                                               k * site_bytes, kFusedLoadAux);
       v[k] = make_uint4(w.x, w.y, w.z, w.w);
     }
-    if (!(ABL & 2)) {
 #pragma unroll
-      for (int p = 0; p < 4; ++p)
-        c[p] = __builtin_bit_cast(float4,
-                                  __builtin_amdgcn_raw_buffer_load_b128(un.rcf, off, p * ngroups * 16, 0));
-    }
+    for (int p = 0; p < 4; ++p)
+      c[p] = __builtin_bit_cast(float4,
+                                __builtin_amdgcn_raw_buffer_load_b128(un.rcf, off, p * ngroups * 16, 0));
   };
 
   uint4 vA[SPU], vB[SPU];
@@ -380,7 +373,6 @@ __global__ __launch_bounds__(NT, (LB * 4 > 80 * 1024 && NT <= 512) ? 2 : 4) void
             msk |= ((t >> 16) ? 2u : 0u) << (2 * p);
           }
           if (PK) rare[k] += __builtin_popcount(msk);
-          if (ABL & 64) msk = 0u;  // (ablation: counted for the wrap check, not staged)
           while (msk) {
             const uint32_t b = __builtin_ctz(msk);
             msk &= msk - 1u;
@@ -460,9 +452,11 @@ __global__ __launch_bounds__(NT, (LB * 4 > 80 * 1024 && NT <= 512) ? 2 : 4) void
       pre = true;
     }
     cur = nxt;
-    if (ABL & 9) continue;
     __syncthreads();
-    if (PK) {
+    if (ABL & 1) {
+      // no histogram: no slices to check, list, flush or recount; the round
+      // masks, the staged fixups and par below are every form's
+    } else if (PK) {
       // the check: each site's counters (a wrapped half comes up 65,536
       // short) plus its global-path pixels against the band's pixel count
       uint32_t sum[SPU];
@@ -649,9 +643,18 @@ static int fused_bands(int cfg_bands, int64_t n_sites, int spu, int64_t n_wgs, i
   return b;
 }
 
-static void launch_correct_hist_cfg(const FusedJobs& J, int64_t npx, int log_transform,
-                                    int clip_lo, int clip_hi, int* queues, int n_wg, int cfg,
-                                    int bands_opt, hipStream_t s) {
+// One launch of configuration cfg over the jobs of J (chosen by the caller:
+// abi_fused.hip picks it per job from the host-read site probe, so no losing
+// configuration is queued).  The caller zeroed queues and every job's uni.
+// The round masks name every non-empty round whatever the configuration, so
+// the histogram finalize is the same.  The "correct_hist" timing bracket
+// holds the kernel alone (the scratch reset is outside it), so the bench's
+// per-launch rate is the pass's own.
+void launch_correct_hist(const FusedJobs& J, int64_t npx, int log_transform, int clip_lo,
+                         int clip_hi, int* queues, int n_wg, int cfg, int bands_opt,
+                         hipStream_t s) {
+  if (J.n <= 0) return;
+  ProfScope prof("correct_hist", s);
   int64_t n_sites = 0;  // the bands see the launch's site groups, every job's
 #define TMH_LAUNCH_CH(L_, K_, A_)                                                                \
   {                                                                                              \
@@ -687,38 +690,6 @@ static void launch_correct_hist_cfg(const FusedJobs& J, int64_t npx, int log_tra
 #undef TMH_LAUNCH_CFG
 #undef TMH_LAUNCH_CH
   TMH_HIP(hipGetLastError());
-}
-
-// One launch of configuration cfg (chosen by the caller: abi.hip picks it per
-// job from the host-read site probe, so no losing configuration is queued).
-// The round masks name every non-empty round whatever the configuration, so
-// the histogram finalize is the same.  The "correct_hist" timing bracket
-// holds the kernel alone (the scratch reset is outside it), so the bench's
-// per-launch rate is the pass's own.
-void launch_correct_hist(const uint16_t* in, uint16_t* out, int64_t npx, int64_t n_sites,
-                         const float2* coef2, const float4* mconst2, const FixList& fl,
-                         int log_transform, int clip_lo, int clip_hi, uint32_t* hist,
-                         unsigned long long* rmask, int* queues, int n_wg, int cfg, int bands,
-                         hipStream_t s, const SiteTab& tab, const RareList& rl) {
-  if (n_sites <= 0) return;
-  // queues[0..8): per-XCD unit counters; queues[8..10): the union of the
-  // sites' round masks (read by the pooled column sum)
-  TMH_HIP(hipMemsetAsync(queues, 0, kFusedQueueInts * sizeof(int), s));
-  FusedJobs J{};
-  J.n = 1;
-  J.j[0] = FusedJob{in, out, n_sites, reinterpret_cast<const float4*>(coef2), mconst2, fl, hist,
-                    rmask, reinterpret_cast<unsigned long long*>(queues + 8), tab, rl};
-  ProfScope prof("correct_hist", s);
-  launch_correct_hist_cfg(J, npx, log_transform, clip_lo, clip_hi, queues, n_wg, cfg, bands, s);
-}
-
-// Several jobs in one launch (the caller zeroed queues and every job's uni).
-void launch_correct_hist_jobs(const FusedJobs& J, int64_t npx, int log_transform, int clip_lo,
-                              int clip_hi, int* queues, int n_wg, int cfg, int bands,
-                              hipStream_t s) {
-  if (J.n <= 0) return;
-  ProfScope prof("correct_hist", s);
-  launch_correct_hist_cfg(J, npx, log_transform, clip_lo, clip_hi, queues, n_wg, cfg, bands, s);
 }
 
 // Each site's rare list into its histogram: one workgroup per site, the

@@ -453,7 +453,7 @@ static void launch_welford_vec8(const uint16_t* sites, int64_t npx, int64_t n_si
                        n_sites, per, mg, mean, m2, lut, part, wide, tab);
 }
 
-// Site probe of a job (tmh_stats' automatic choices, abi.hip): of kProbeGroups
+// Site probe of a job (tmh_stats' automatic choices, abi_stats.hip): of kProbeGroups
 // 8-pixel groups spread over the launch's first min(n, kProbeSites) sites, how
 // many hold a value >= 4,096 (out[1]) and >= 16,384 (out[2]); out[0] = the
 // groups sampled.  One workgroup, every load in flight at once (one DRAM

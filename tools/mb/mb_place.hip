@@ -121,26 +121,23 @@ static int run(int argc, char** argv) {
     }
     return tot / reps;
   };
-  auto fused = [&](int i, int o) {
-    return time([&] {
-      CK(hipMemsetAsync(fn, 0, 4, 0));
-      // zero-maintained slab: the production finalize resets it; here a memset
-      CK(hipMemsetAsync(rmask, 0, S * 8, 0));
-      launch_correct_hist(buf[i], buf[o], npx, S, (const float2*)coef, mconst2, fl, 1, -1, -1, hist,
-                          rmask, queues, cus, kFusedNarrow, 0, 0);
-    });
-  };
   // output written at buf[o] + delta bytes: does the read/write address
   // relation matter?
   auto fused_at = [&](int i, int o, size_t delta) {
     return time([&] {
       CK(hipMemsetAsync(fn, 0, 4, 0));
+      // zero-maintained slab: the production finalize resets it; here a memset
       CK(hipMemsetAsync(rmask, 0, S * 8, 0));
-      launch_correct_hist(buf[i], reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(buf[o]) + delta),
-                          npx, S, (const float2*)coef, mconst2, fl, 1, -1, -1, hist, rmask, queues,
-                          cus, kFusedNarrow, 0, 0);
+      CK(hipMemsetAsync(queues, 0, kFusedQueueInts * sizeof(int), 0));
+      FusedJobs J{};
+      J.n = 1;
+      J.j[0] = FusedJob{buf[i], reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(buf[o]) + delta),
+                        S, coef, mconst2, fl, hist, rmask,
+                        reinterpret_cast<unsigned long long*>(queues + 8), SiteTab{}, RareList{}};
+      launch_correct_hist(J, npx, 1, -1, -1, queues, cus, kFusedNarrow, 0, 0);
     });
   };
+  auto fused = [&](int i, int o) { return fused_at(i, o, 0); };
   auto welford = [&](int i) {
     return time([&] {
       launch_welford(buf[i], npx, S, 0, rn, mean, m2, lut, 1, part, 8 * npx, 1, wide, 0, 0);

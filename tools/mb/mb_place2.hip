@@ -133,8 +133,12 @@ int main(int argc, char** argv) {
       return time([&] {
         CK(hipMemsetAsync(fn, 0, 4, 0));
         CK(hipMemsetAsync(rmask, 0, S * 8, 0));
-        launch_correct_hist(in, out, npx, S, (const float2*)coef, mconst2, fl, 1, -1, -1, hist,
-                            rmask, queues, cus, kFusedNarrow, 0, 0, tab);
+        CK(hipMemsetAsync(queues, 0, kFusedQueueInts * sizeof(int), 0));
+        FusedJobs J{};
+        J.n = 1;
+        J.j[0] = FusedJob{in, out, S, coef, mconst2, fl, hist, rmask,
+                          reinterpret_cast<unsigned long long*>(queues + 8), tab, RareList{}};
+        launch_correct_hist(J, npx, 1, -1, -1, queues, cus, kFusedNarrow, 0, 0);
       });
     };
     double *mean, *m2, *lut, *rn, *part;

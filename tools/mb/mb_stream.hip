@@ -296,12 +296,6 @@ int main(int argc, char** argv) {
              [&] { fusedp(k_correct_hist<true, false, 4, 0, 1024, 65536, true>, 8); });
         time("packed abl0 16 bands", cbytes,
              [&] { fusedp(k_correct_hist<true, false, 4, 0, 1024, 65536, true>, 16); });
-        time("packed abl8 (no flush)", cbytes,
-             [&] { fusedp(k_correct_hist<true, false, 4, 8, 1024, 65536, true>, 8); });
-        time("packed abl64 (no rare path)", cbytes,
-             [&] { fusedp(k_correct_hist<true, false, 4, 64, 1024, 65536, true>, 8); });
-        time("packed abl96 (no rare, no arith)", cbytes,
-             [&] { fusedp(k_correct_hist<true, false, 4, 96, 1024, 65536, true>, 8); });
       }
       printf("done\n");
       return 0;

@@ -117,8 +117,12 @@ static int run(int argc, char** argv) {
   const FixList fl{fe, fn, (unsigned)(((size_t)1 << 23) / 8)};
   int* queues;  // per-XCD unit counters + round-mask union
   CK(hipMalloc(&queues, kFusedQueueInts * sizeof(int)));
-  launch_correct_hist(in, out, npx, S, (const float2*)coef, mconst2, fl, 1, -1, -1, hist, rmask,
-                      queues, cus, dist == 0 ? kFusedNarrow : kFusedWide, 0, 0);
+  CK(hipMemset(queues, 0, kFusedQueueInts * sizeof(int)));
+  FusedJobs J{};
+  J.n = 1;
+  J.j[0] = FusedJob{in, out, S, coef, mconst2, fl, hist, rmask,
+                    reinterpret_cast<unsigned long long*>(queues + 8), SiteTab{}, RareList{}};
+  launch_correct_hist(J, npx, 1, -1, -1, queues, cus, dist == 0 ? kFusedNarrow : kFusedWide, 0, 0);
   CK(hipDeviceSynchronize());
   {
     std::vector<unsigned long long> rm(S);
