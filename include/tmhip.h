@@ -814,6 +814,66 @@ int tmh_object_table_device(const int32_t* dev_planes, int64_t n_planes, int hei
 int tmh_object_table(const int32_t* host_planes, int64_t n_planes, int height, int width,
                      int32_t* max_label, tmh_object_row* host_rows, int64_t row_capacity);
 
+/* SegmentationImage.extract_polygons (tmlib/image.py:778-917) up to its choice
+ * of shell and holes: per label of a plane, the mask of the label inside its
+ * bounding box padded by one pixel, taken from the plane with row 0, row H-1,
+ * column 0 and column W-1 zeroed; mh.open (the 3x3 cross) when the mask has
+ * more than one pixel; then every border cv2.findContours(RETR_CCOMP,
+ * CHAIN_APPROX_NONE) follows, as Suzuki and Abe's Algorithm 1 defines them.
+ * Points are (x, y) = (column, row) of the padded mask, int32 pairs; the
+ * caller adds the offsets (image.py:886-893).  A box of more than
+ * TMH_CONTOUR_LDS_PIXELS padded pixels is traced in memory instead of LDS:
+ * slower, the same result; up to TMH_CONTOUR_LDS_SMALL_PIXELS and up to
+ * TMH_CONTOUR_LDS_TINY_PIXELS it takes smaller LDS forms. */
+#define TMH_CONTOUR_LDS_PIXELS 16384
+#define TMH_CONTOUR_LDS_SMALL_PIXELS 4096
+#define TMH_CONTOUR_LDS_TINY_PIXELS 1024
+typedef struct tmh_contour {
+  int32_t plane, label;
+  int32_t is_hole;        /* 0: outer border, 1: hole border */
+  int32_t parent;         /* a hole's outer border, as an index among the object's contours; else -1 */
+  int64_t point_offset;   /* first point, as an index among all points of the call */
+  int64_t n_points;
+} tmh_contour;
+typedef struct tmh_contour_object {
+  int32_t plane, label;
+  int64_t first_contour, first_point;  /* exclusive scans in (plane, label) order */
+  int32_t n_contours;     /* in discovery order (raster scan); 0: the opening left nothing */
+  int32_t opened;         /* the mask had more than one pixel, so mh.open ran */
+  int64_t n_points;
+  int64_t n_interior;     /* pixels of the label off the four border lines; 0: the label yields nothing */
+  int64_t sum_y, sum_x;   /* their plane coordinates summed (image.py:835-836) */
+} tmh_contour_object;
+/* dev_rows: what tmh_object_table_device wrote for the same planes and
+ * max_label (the planes are not read again for their label range).
+ * dev_objects [n_planes][max_label + 1] is always filled; *n_contours and
+ * *n_points (host) are the totals.  dev_contours and dev_points NULL: the call
+ * only measures.  Otherwise object o's borders are dev_contours[first_contour
+ * .. + n_contours) and its points dev_points[2 * first_point ..): one compact
+ * table in (plane, label, discovery) order, identical bytes from call to call;
+ * a capacity below the totals: TMH_EINVAL with the totals set and nothing
+ * written to either.  Objects are traced once to measure and, when writing,
+ * once more at their offsets; work is queued on `stream` (NULL: the default
+ * stream) and the call returns when the result is complete. */
+int tmh_object_contours_device(const int32_t* dev_planes, int64_t n_planes, int height, int width,
+                               int32_t max_label, const tmh_object_row* dev_rows,
+                               tmh_contour_object* dev_objects, tmh_contour* dev_contours,
+                               int64_t contour_capacity, int32_t* dev_points,
+                               int64_t point_capacity, int64_t* n_contours, int64_t* n_points,
+                               void* stream);
+/* Host buffers: the object table and the contours of host planes in one call.
+ * *max_label, *n_contours and *n_points are what the planes need; host_rows
+ * and host_objects hold row_capacity entries each (n_planes * (*max_label + 1)
+ * needed), host_contours contour_capacity, host_points 2 * point_capacity
+ * int32.  Any capacity too small (or its pointer NULL): TMH_EINVAL with the
+ * three counts set and nothing written.  A negative label: TMH_EINVAL. */
+int tmh_object_contours(const int32_t* host_planes, int64_t n_planes, int height, int width,
+                        int32_t* max_label, tmh_object_row* host_rows,
+                        tmh_contour_object* host_objects, int64_t row_capacity,
+                        tmh_contour* host_contours, int64_t contour_capacity,
+                        int32_t* host_points, int64_t point_capacity, int64_t* n_contours,
+                        int64_t* n_points);
+
 /* ---- device memory helpers for callers without another allocator -------- */
 int tmh_malloc_device(void** dev_ptr, size_t bytes);
 int tmh_free_device(void* dev_ptr);

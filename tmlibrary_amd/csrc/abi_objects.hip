@@ -1,5 +1,6 @@
 // C-ABI of libtmhip.so (include/tmhip.h): jterator object tables -- label
-// range and the per-label integer sums of int32 label planes.
+// range and the per-label integer sums of int32 label planes -- and the
+// objects' outlines (extract_polygons' contours).
 #include <climits>
 
 #include "abi_internal.h"
@@ -56,6 +57,40 @@ static void object_table_dev(const int32_t* dev_planes, int64_t n_planes, int he
                       (hipStream_t)stream);
 }
 
+static int64_t contour_rows(int64_t n_planes, int32_t max_label) {
+  const int64_t n_rows = n_planes * ((int64_t)max_label + 1);
+  TMH_CHECK(n_rows <= INT_MAX, TMH_EINVAL, "at most 2^31 - 1 (plane, label) rows per call");
+  return n_rows;
+}
+
+// the two-call contract of tmh_object_contours_device; the host form passes
+// the capacity of its rows too (row_capacity < 0: none to check)
+static void object_contours_dev(const int32_t* dev_planes, int64_t n_planes, int height, int width,
+                                int32_t max_label, const tmh_object_row* dev_rows,
+                                tmh_contour_object* dev_objects, tmh_contour* dev_contours,
+                                int64_t contour_capacity, int32_t* dev_points,
+                                int64_t point_capacity, int64_t* n_contours, int64_t* n_points,
+                                void* stream) {
+  check_planes_args(dev_planes, n_planes, height, width);
+  TMH_CHECK(max_label >= 0, TMH_EINVAL, "max_label is negative");
+  TMH_CHECK(n_contours && n_points, TMH_EINVAL, "n_contours or n_points pointer is NULL");
+  *n_contours = *n_points = 0;
+  if (n_planes == 0) return;
+  TMH_CHECK(dev_rows && dev_objects, TMH_EINVAL, "rows or objects pointer is NULL");
+  TMH_CHECK((dev_contours == nullptr) == (dev_points == nullptr), TMH_EINVAL,
+            "contours and points are given together or not at all");
+  TMH_CHECK(contour_capacity >= 0 && point_capacity >= 0, TMH_EINVAL, "negative capacity");
+  contour_rows(n_planes, max_label);
+  ContourScratch scratch;
+  contours_measure(dev_planes, n_planes, height, width, max_label, dev_rows, dev_objects, scratch,
+                   n_contours, n_points, (hipStream_t)stream);
+  if (!dev_contours) return;
+  TMH_CHECK(contour_capacity >= *n_contours && point_capacity >= *n_points, TMH_EINVAL,
+            "contour or point capacity smaller than *n_contours, *n_points");
+  contours_write(dev_planes, height, width, max_label, dev_rows, dev_objects, scratch, dev_contours,
+                 dev_points, (hipStream_t)stream);
+}
+
 }  // namespace tmh
 
 extern "C" {
@@ -94,6 +129,65 @@ int tmh_object_table(const int32_t* host_planes, int64_t n_planes, int height, i
     object_table_dev(a.p, n_planes, height, width, hi, rows.p, nullptr, true);
     TMH_HIP(hipStreamSynchronize(nullptr));
     rows.download(host_rows, (size_t)n_rows);
+  });
+}
+
+int tmh_object_contours_device(const int32_t* dev_planes, int64_t n_planes, int height, int width,
+                               int32_t max_label, const tmh_object_row* dev_rows,
+                               tmh_contour_object* dev_objects, tmh_contour* dev_contours,
+                               int64_t contour_capacity, int32_t* dev_points,
+                               int64_t point_capacity, int64_t* n_contours, int64_t* n_points,
+                               void* stream) {
+  return guard([&] {
+    object_contours_dev(dev_planes, n_planes, height, width, max_label, dev_rows, dev_objects,
+                        dev_contours, contour_capacity, dev_points, point_capacity, n_contours,
+                        n_points, stream);
+  });
+}
+
+int tmh_object_contours(const int32_t* host_planes, int64_t n_planes, int height, int width,
+                        int32_t* max_label, tmh_object_row* host_rows,
+                        tmh_contour_object* host_objects, int64_t row_capacity,
+                        tmh_contour* host_contours, int64_t contour_capacity,
+                        int32_t* host_points, int64_t point_capacity, int64_t* n_contours,
+                        int64_t* n_points) {
+  return guard([&] {
+    check_planes_args(host_planes, n_planes, height, width);
+    TMH_CHECK(max_label && n_contours && n_points, TMH_EINVAL, "a count pointer is NULL");
+    *max_label = 0;
+    *n_contours = *n_points = 0;
+    if (n_planes == 0) return;
+    DBuf<int32_t> a;
+    a.upload(host_planes, (size_t)n_planes * height * width);
+    int32_t hi, lo;
+    label_range(a.p, n_planes, height, width, nullptr, &hi, &lo);
+    TMH_CHECK(lo >= 0, TMH_EINVAL, "a label plane holds a negative label");
+    *max_label = hi;
+    const int64_t n_rows = contour_rows(n_planes, hi);
+    DBuf<tmh_object_row> rows;
+    rows.alloc((size_t)n_rows);
+    DBuf<tmh_contour_object> objects;
+    objects.alloc((size_t)n_rows);
+    object_table_dev(a.p, n_planes, height, width, hi, rows.p, nullptr, true);
+    // measure, check every capacity before anything is written, then fill
+    object_contours_dev(a.p, n_planes, height, width, hi, rows.p, objects.p, nullptr, 0, nullptr, 0,
+                        n_contours, n_points, nullptr);
+    TMH_CHECK(host_rows && host_objects && row_capacity >= n_rows, TMH_EINVAL,
+              "row capacity smaller than n_planes * (*max_label + 1) rows");
+    TMH_CHECK(contour_capacity >= *n_contours && point_capacity >= *n_points &&
+                  (host_contours || *n_contours == 0) && (host_points || *n_points == 0),
+              TMH_EINVAL, "contour or point capacity smaller than *n_contours, *n_points");
+    DBuf<tmh_contour> contours;
+    contours.alloc((size_t)std::max<int64_t>(*n_contours, 1));
+    DBuf<int32_t> points;
+    points.alloc((size_t)std::max<int64_t>(2 * *n_points, 2));
+    int64_t nc = 0, np = 0;
+    object_contours_dev(a.p, n_planes, height, width, hi, rows.p, objects.p, contours.p, *n_contours,
+                        points.p, *n_points, &nc, &np, nullptr);
+    rows.download(host_rows, (size_t)n_rows);
+    objects.download(host_objects, (size_t)n_rows);
+    if (nc) contours.download(host_contours, (size_t)nc);
+    if (np) points.download(host_points, (size_t)(2 * np));
   });
 }
 

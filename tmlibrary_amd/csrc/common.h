@@ -459,6 +459,28 @@ void launch_label_minmax(const int32_t* planes, int64_t n_planes, int64_t npx, i
                          int32_t* d_min, hipStream_t s);
 void launch_object_table(const int32_t* planes, int64_t n_planes, int H, int W, int32_t max_label,
                          tmh_object_row* rows, hipStream_t s);
+// jterator object outlines (contour_kernels.hip): the count pass and scan,
+// then the write pass on the same arguments; the scratch lives across both
+struct ContourScratch {
+  int32_t* lists = nullptr;     // rows whose box fits no LDS form, the large one, the small one
+  void* dims = nullptr;
+  uint64_t* ws = nullptr;       // their workspace
+  int64_t n_rows = 0;
+  unsigned long long words = 0, pixels = 0;
+  unsigned int n_list[3] = {0u, 0u, 0u};
+  ContourScratch() = default;
+  ContourScratch(const ContourScratch&) = delete;
+  ContourScratch& operator=(const ContourScratch&) = delete;
+  ~ContourScratch();
+};
+void contours_measure(const int32_t* planes, int64_t n_planes, int H, int W, int32_t max_label,
+                      const tmh_object_row* rows, tmh_contour_object* objects,
+                      ContourScratch& scratch, int64_t* n_contours, int64_t* n_points,
+                      hipStream_t s);
+void contours_write(const int32_t* planes, int H, int W, int32_t max_label,
+                    const tmh_object_row* rows, tmh_contour_object* objects,
+                    const ContourScratch& scratch, tmh_contour* contours, int32_t* points,
+                    hipStream_t s);
 // site-image input (inflate_kernels.hip)
 int64_t inflate_scratch_bytes(int64_t n_chunks, int64_t raw_max);
 void launch_inflate(const uint8_t* src, int64_t src_bytes, const tmh_zchunk* chunks,

@@ -137,6 +137,10 @@ SIGNATURES = {
     "tmh_label_max_device": (_I, [_P, _I64, _I, _I, _P, _P, _P]),
     "tmh_object_table_device": (_I, [_P, _I64, _I, _I, C.c_int32, _P, _P]),
     "tmh_object_table": (_I, [_P, _I64, _I, _I, C.POINTER(C.c_int32), _P, _I64]),
+    "tmh_object_contours_device": (_I, [_P, _I64, _I, _I, C.c_int32, _P, _P, _P, _I64, _P, _I64,
+                                        C.POINTER(_I64), C.POINTER(_I64), _P]),
+    "tmh_object_contours": (_I, [_P, _I64, _I, _I, C.POINTER(C.c_int32), _P, _P, _I64, _P, _I64, _P,
+                                 _I64, C.POINTER(_I64), C.POINTER(_I64)]),
     "tmh_malloc_device": (_I, [C.POINTER(_P), C.c_size_t]),
     "tmh_free_device": (_I, [_P]),
     "tmh_memcpy": (_I, [_P, _P, C.c_size_t, _I, _P]),
@@ -162,6 +166,25 @@ OBJECT_ROW_DTYPE = np.dtype([("n", np.int64), ("sum_y", np.int64), ("sum_x", np.
                              ("y0", np.int32), ("y1", np.int32), ("x0", np.int32),
                              ("x1", np.int32), ("border", np.int32), ("pad", np.int32)])
 assert OBJECT_ROW_DTYPE.itemsize == 48
+
+
+#: struct tmh_contour (include/tmhip.h): one border of one object
+CONTOUR_DTYPE = np.dtype([("plane", np.int32), ("label", np.int32), ("is_hole", np.int32),
+                          ("parent", np.int32), ("point_offset", np.int64),
+                          ("n_points", np.int64)])
+assert CONTOUR_DTYPE.itemsize == 32
+#: struct tmh_contour_object (include/tmhip.h): one (plane, label) of a contour call
+CONTOUR_OBJECT_DTYPE = np.dtype([("plane", np.int32), ("label", np.int32),
+                                 ("first_contour", np.int64), ("first_point", np.int64),
+                                 ("n_contours", np.int32), ("opened", np.int32),
+                                 ("n_points", np.int64), ("n_interior", np.int64),
+                                 ("sum_y", np.int64), ("sum_x", np.int64)])
+assert CONTOUR_OBJECT_DTYPE.itemsize == 64
+#: TMH_CONTOUR_LDS_PIXELS: padded boxes above this many pixels are traced in memory;
+#: TMH_CONTOUR_LDS_SMALL_PIXELS / _TINY_PIXELS: up to these they take smaller LDS forms
+CONTOUR_LDS_PIXELS = 16384
+CONTOUR_LDS_SMALL_PIXELS = 4096
+CONTOUR_LDS_TINY_PIXELS = 1024
 
 
 #: struct tmh_zchunk (include/tmhip.h): one HDF5 gzip chunk of the input path

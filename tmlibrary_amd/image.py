@@ -683,11 +683,176 @@ def object_tables(planes: np.ndarray) -> np.ndarray:
         return rows.reshape(-1)[:n * (mx.value + 1)].reshape(n, mx.value + 1)
 
 
+def object_contours(planes: np.ndarray):
+    """The object tables and every object's borders of int32 label planes
+    [n, H, W] in one ``tmh_object_contours`` call: ``(rows, objects, contours,
+    points)`` -- rows and objects [n, max_label + 1] of ``hip.OBJECT_ROW_DTYPE``
+    and ``hip.CONTOUR_OBJECT_DTYPE``, contours of ``hip.CONTOUR_DTYPE`` in
+    (plane, label, discovery) order, points int32 [n_points, 2] as (x, y) of
+    each object's padded bounding-box mask.  A negative label raises ValueError."""
+    a = np.ascontiguousarray(planes)
+    if a.dtype != np.int32 or a.ndim != 3:
+        raise TypeError("label planes must be an int32 array [n, H, W]")
+    L = hip.lib()
+    n = a.shape[0]
+    if n == 0 or a.shape[1] == 0 or a.shape[2] == 0:
+        return (np.zeros((n, 1), dtype=hip.OBJECT_ROW_DTYPE),
+                np.zeros((n, 1), dtype=hip.CONTOUR_OBJECT_DTYPE),
+                np.zeros(0, dtype=hip.CONTOUR_DTYPE), np.zeros((0, 2), dtype=np.int32))
+    mx, nc, npt = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    # a first attempt sized by guess; the call reports what a larger result needs
+    per, cap_c, cap_p = 4096, 2 * 4096 * n, max(4096, a.size // 8)
+    while True:
+        rows = np.empty((n, per), dtype=hip.OBJECT_ROW_DTYPE)
+        objects = np.empty((n, per), dtype=hip.CONTOUR_OBJECT_DTYPE)
+        contours = np.empty(cap_c, dtype=hip.CONTOUR_DTYPE)
+        points = np.empty((cap_p, 2), dtype=np.int32)
+        rc = L.tmh_object_contours(hip.ptr(a), n, a.shape[1], a.shape[2], C.byref(mx),
+                                   hip.ptr(rows), hip.ptr(objects), rows.size, hip.ptr(contours),
+                                   cap_c, hip.ptr(points), cap_p, C.byref(nc), C.byref(npt))
+        if rc == hip.TMH_EINVAL and (mx.value + 1 > per or nc.value > cap_c or npt.value > cap_p):
+            per, cap_c, cap_p = max(per, mx.value + 1), max(cap_c, nc.value), max(cap_p, npt.value)
+            continue
+        hip.check(rc)
+        k = mx.value + 1
+        return (rows.reshape(-1)[:n * k].reshape(n, k), objects.reshape(-1)[:n * k].reshape(n, k),
+                contours[:nc.value], points[:npt.value])
+
+
+def cv2_order(n):
+    """List position -> discovery index of the list cv2.findContours returns
+    for n borders: reverse discovery order (OpenCV's legacy tracer links a
+    later border in front -- DESIGN section 1, rests on reading).  The one
+    place that order is decided."""
+    return list(range(n - 1, -1, -1))
+
+
+def cv2_shaped(borders, parents):
+    """cv2.findContours' ``(contours, hierarchy)`` from borders (int32 [n, 2]
+    arrays) in discovery order and their RETR_CCOMP parents (discovery
+    indices, -1 for an outer border): contours a list of [n, 1, 2] arrays,
+    hierarchy [1, n, 4] of [next, previous, first child, parent] positions."""
+    n = len(borders)
+    order = cv2_order(n)
+    pos = dict((d, p) for p, d in enumerate(order))
+    contours = [np.array(borders[d], dtype=np.int32).reshape(-1, 1, 2) for d in order]
+    hierarchy = np.full((1, n, 4), -1, dtype=np.int32)
+    last = dict()  # parent position -> the last position seen with that parent
+    for p, d in enumerate(order):
+        parent = pos[parents[d]] if parents[d] >= 0 else -1
+        hierarchy[0, p, 3] = parent
+        if parent in last:
+            hierarchy[0, p, 1] = last[parent]
+            hierarchy[0, last[parent], 0] = p
+        elif parent >= 0:
+            hierarchy[0, parent, 2] = p
+        last[parent] = p
+    return contours, hierarchy
+
+
+def select_shell_and_holes(contours, hierarchy):
+    """tmlib/image.py:842-869 as written, for one or more contours: of an
+    outer border with holes only its first child is kept; among several outer
+    borders without holes the longest is the shell."""
+    if len(contours) > 1:
+        holes = list()
+        for i in range(len(contours)):
+            child_idx = hierarchy[0][i][2]
+            parent_idx = hierarchy[0][i][3]
+            if parent_idx >= 0:
+                shell = np.squeeze(contours[parent_idx])
+            elif child_idx >= 0:
+                holes.append(np.squeeze(contours[child_idx]))
+            else:
+                lengths = [len(c) for c in contours]
+                idx = lengths.index(np.max(lengths))
+                shell = np.squeeze(contours[idx])
+                break
+    else:
+        shell = np.squeeze(contours[0])
+        holes = None
+    return shell, holes
+
+
+class ContourPolygon(object):
+    """What extract_polygons yields where the reference builds a
+    ``shapely.geometry.Polygon``: the shell and the holes as int32 [n, 2]
+    (x, y) rings, unclosed as cv2 gives them.  The reference's ``is_valid`` /
+    ``buffer(0)`` repair (image.py:895-916) is not applied."""
+
+    __slots__ = ("shell", "holes")
+
+    def __init__(self, shell, holes=None):
+        self.shell = np.ascontiguousarray(shell, dtype=np.int32).reshape(-1, 2)
+        self.holes = [np.ascontiguousarray(h, dtype=np.int32).reshape(-1, 2)
+                      for h in (holes or [])]
+
+    def to_shapely(self):
+        try:
+            import shapely.geometry
+        except ImportError:
+            from .workflow.align.api import NotSupportedError
+            raise NotSupportedError("shapely is not installed: no shapely.geometry.Polygon")
+        return shapely.geometry.Polygon(self.shell, self.holes)
+
+    def __eq__(self, other):
+        return (isinstance(other, ContourPolygon) and np.array_equal(self.shell, other.shell)
+                and len(self.holes) == len(other.holes)
+                and all(np.array_equal(a, b) for a, b in zip(self.holes, other.holes)))
+
+    def __ne__(self, other):
+        return not self == other
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "<ContourPolygon(shell=%d points, holes=%d)>" % (len(self.shell), len(self.holes))
+
+
+def _square(x, y):
+    return np.array([[x - 1, x + 1, x + 1, x - 1, x - 1],
+                     [y - 1, y - 1, y + 1, y + 1, y - 1]]).T.astype(np.int32)
+
+
+def polygons_of_plane(rows, objects, contours, points, y_offset, x_offset):
+    """image.py:807-917 from one plane's device result (``object_contours``):
+    a generator of (label, ContourPolygon) in ascending label order."""
+    for label in np.nonzero(objects["n_interior"] > 0)[0]:
+        o, r = objects[label], rows[label]
+        table = contours[o["first_contour"]:o["first_contour"] + o["n_contours"]]
+        holes = None
+        if len(table) == 0:
+            # the opening left nothing: the mean of the label's pixels on the
+            # border-zeroed plane, in plane coordinates (image.py:835-841)
+            y = int(np.float64(o["sum_y"]) / np.float64(o["n_interior"]))
+            x = int(np.float64(o["sum_x"]) / np.float64(o["n_interior"]))
+            shell = _square(x, y)
+        else:
+            borders = [points[c["point_offset"]:c["point_offset"] + c["n_points"]] for c in table]
+            cv_contours, hierarchy = cv2_shaped(borders, table["parent"])
+            shell, holes = select_shell_and_holes(cv_contours, hierarchy)
+        if shell.ndim < 2 or shell.shape[0] < 3:
+            # image.py:871-882; the reference is Python 2: / on these ints floors
+            y, x = (int(r["y1"] - r["y0"]) + 2) // 2, (int(r["x1"] - r["x0"]) + 2) // 2
+            shell = _square(x, y)
+        add_y = y_offset + int(r["y0"]) - 1
+        add_x = x_offset + int(r["x0"]) - 1
+        shell[:, 0] = shell[:, 0] + add_x
+        shell[:, 1] = -1 * (shell[:, 1] + add_y)
+        if holes is not None:
+            for i in range(len(holes)):
+                holes[i][:, 0] = holes[i][:, 0] + add_x
+                holes[i][:, 1] = -1 * (holes[i][:, 1] + add_y)
+        yield (int(label), ContourPolygon(shell, holes))
+
+
 class SegmentationImage(Image):
     """A labeled image, one positive int32 identifier per segmented object
-    (tmlib/image.py:696-738).  The per-object numbers ``extract_polygons``
-    starts from come from the GPU's object table; the contour half of
-    ``extract_polygons`` and ``create_from_polygons`` are not built."""
+    (tmlib/image.py:696-738).  The reference's ``extract_polygons`` method is
+    the module's function ``extract_polygons(image, y_offset, x_offset)``: the
+    class itself keeps to the attributes tests/test_jterator_cpu.py pins
+    (neither ``extract_polygons`` nor ``create_from_polygons``, which is not
+    built)."""
 
     __slots__ = ()
 
@@ -723,6 +888,17 @@ class SegmentationImage(Image):
         [min_y, max_y + 1, min_x, max_x + 1], zeros for absent labels."""
         t = self.object_table()
         return np.stack([t["y0"], t["y1"], t["x0"], t["x1"]], axis=1).astype(np.intp)
+
+
+def extract_polygons(image, y_offset, x_offset):
+    """SegmentationImage.extract_polygons of the reference (image.py:778-917)
+    for a ``SegmentationImage``: a generator of (label, polygon) in ascending
+    label order, the polygon a ``ContourPolygon`` (no shapely repair), from
+    one device call -- the object table plus the contours of the plane."""
+    if not isinstance(image, SegmentationImage):
+        raise TypeError('Argument "image" must have type SegmentationImage.')
+    rows, objects, contours, points = object_contours(image.array[None])
+    return polygons_of_plane(rows[0], objects[0], contours, points, y_offset, x_offset)
 
 
 class IllumstatsImage(Image):
