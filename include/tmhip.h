@@ -353,6 +353,11 @@ int tmh_job_planes_multi_device(tmh_stats* const* hs, tmh_corrector* const* cs, 
  * complete; host_out must not overlap host_in. */
 int tmh_correct_u16(tmh_corrector* c, const uint16_t* host_in, uint16_t* host_out,
                     int64_t n_sites, int clip_lo, int clip_hi);
+/* Device buffers, queued on `stream` (NULL: the corrector's).  dev_in and
+ * dev_out must not overlap: the f64 refinement re-reads the input pixels it
+ * redoes after the streaming kernel has stored the output, so an in-place
+ * call would correct those pixels twice.  Overlapping ranges are rejected
+ * with TMH_EINVAL, nothing launched. */
 int tmh_correct_u16_device(tmh_corrector* c, const uint16_t* dev_in, uint16_t* dev_out,
                            int64_t n_sites, int clip_lo, int clip_hi, void* stream);
 /* Correct n_sites pending sites of h and fold their histograms/percentiles
@@ -768,7 +773,7 @@ int tmh_zproject_max(const void* host_planes, int64_t n_sites, int z, int height
  * slot); a window whose rows / cols differ from (out_h, out_w) (the
  * reference's numpy assignment raises there) or which leaves the source; a
  * site or slot index out of range; a corrector of another image size; more
- * than 65,535 sites.  dev_out must not overlap dev_in; both are 2-byte
+ * than 65,535 sites; dev_out overlapping dev_in.  Both are 2-byte
  * aligned (the 16-byte forms of slots == 1 want dev_in, corrected, or
  * dev_out, not corrected, 16-byte aligned).  Queued on `stream` (NULL: the
  * corrector's, or the default stream without one); the call returns when the
@@ -788,7 +793,13 @@ int tmh_correct_stack_u16(tmh_corrector* c, const uint16_t* host_in, uint16_t* h
  * (mh.center_of_mass(plane, labels=plane)) and is_border, one row per label
  * 0..max_label of one int32 label plane [height][width] (label 0, the
  * background, gets a row like any other; mahotas does the same).  Every field
- * is exact and independent of scheduling. */
+ * is exact and independent of scheduling.  The table kernel gathers each
+ * 16 x 512 tile's labels in an LDS hash of TMH_OBJECT_SLOTS entries (the top
+ * 9 bits of label * 2654435761 mod 2^32, linear probing); a label that finds
+ * no entry within TMH_OBJECT_PROBE probes is added to its row in memory
+ * directly: slower, the same result. */
+#define TMH_OBJECT_SLOTS 512
+#define TMH_OBJECT_PROBE 16
 typedef struct tmh_object_row {
   int64_t n, sum_y, sum_x;  /* pixel count, sum of row indices, sum of column indices */
   int32_t y0, y1, x0, x1;   /* mh.labeled.bbox: [min_y, max_y+1, min_x, max_x+1]; n == 0: all 0 */

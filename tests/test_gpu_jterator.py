@@ -299,6 +299,124 @@ def test_objects_full_size_single_label(L):
     assert got[0][1]["sum_x"] == 2160 * (2560 * 2559 // 2) > 2 ** 32
 
 
+# The table kernel's memory route (objects_kernels.hip k_object_table: a label
+# that finds no LDS entry within TMH_OBJECT_PROBE probes goes through
+# object_add_global to its row in memory).  Which labels of a full tile get the
+# entries depends on the order the waves run in; that more labels than entries
+# take memory does not.
+
+def tile_label_counts(plane):
+    """{(tile row, tile column): distinct labels} of k_object_table's 16 x 512 tiles."""
+    return {(ty, tx): len(np.unique(plane[16 * ty:16 * ty + 16, 512 * tx:512 * tx + 512]))
+            for ty in range(-(-plane.shape[0] // 16)) for tx in range(-(-plane.shape[1] // 512))}
+
+
+def one_label_per_pixel():
+    """(1, 16, 512): one tile, the labels 1..8192 in a random order."""
+    return (np.random.RandomState(61).permutation(8192) + 1).astype(np.int32).reshape(1, 16, 512)
+
+
+def test_objects_one_label_per_pixel(L):
+    """k_object_table's else branch (object_add_global from the pixel loop): a
+    single tile with 8,192 labels and 512 LDS entries, so at least 7,680 labels
+    are added to rows still holding k_object_init's INT_MAX / -1 bounds; every
+    field of every row against the literal, the border flags included (1,052
+    labels lie on the plane's edge)."""
+    from tmlibrary_amd import hip
+    planes = one_label_per_pixel()
+    assert tile_label_counts(planes[0]) == {(0, 0): 8192} and 8192 > hip.OBJECT_SLOTS
+    got = check_tables(planes)
+    assert int(got[0]["border"].sum()) == 2 * 512 + 2 * 14
+    assert np.array_equal(got[0]["n"][1:], np.ones(8192, np.int64))
+
+
+def test_objects_mixed_routes_across_tiles(L):
+    """k_object_table, both routes into the same rows: three planes of 33 x
+    1030 (3 x 3 ragged tiles each) with a label in every pixel, runs of length
+    one, up to 3,000 labels.  The four 16 x 512 tiles of each plane hold more
+    labels than the LDS table has entries, so each sends its surplus through
+    object_add_global; the narrow and the one-row tiles hold few enough to
+    keep theirs in LDS (at most TMH_OBJECT_PROBE labels: certainly), and their
+    labels recur in the full tiles, so rows take flushed LDS entries and direct
+    adds alike.  Planes 1 and 2 have label sets of their own and write at row
+    offset plane * (max_label + 1); labels sit on all four edges."""
+    from tmlibrary_amd import hip
+    H, W = 33, 1030
+    idx = np.arange(H * W, dtype=np.int64).reshape(H, W)
+    rng = np.random.RandomState(62)
+    planes = np.stack([idx * 7919 % 3000 + 1,
+                       idx * 7919 % 2500 + 401,
+                       rng.randint(1001, 3001, (H, W))]).astype(np.int32)
+    assert planes.max() == 3000 and planes.min() >= 1
+    for p in range(3):
+        counts = tile_label_counts(planes[p])
+        assert len(counts) == 9
+        full = [counts[(ty, tx)] for ty in (0, 1) for tx in (0, 1)]
+        assert min(full) > hip.OBJECT_SLOTS, full
+        assert counts[(2, 2)] <= hip.OBJECT_PROBE  # the 1 x 6 corner: LDS for certain
+        corner = set(planes[p][32:, 1024:].ravel().tolist())
+        assert corner <= set(planes[p][:32, :1024].ravel().tolist())
+    assert len({frozenset(np.unique(pl).tolist()) for pl in planes}) == 3
+    got = check_tables(planes)
+    for p in range(3):
+        edge = np.unique(np.concatenate([planes[p][0], planes[p][-1], planes[p][:, 0],
+                                         planes[p][:, -1]]))
+        assert got[p]["border"][edge].all() and int(got[p]["border"].sum()) == len(edge)
+
+
+def same_bucket_labels(bucket, count):
+    """The first `count` labels whose LDS hash is `bucket`.  The hash restated
+    here ((label * 2654435761 mod 2**32) >> (32 - log2(slots)), objects_kernels.hip)
+    is a condition on the input: with another hash the labels would spread over
+    the table and the test would pass without reaching the probe limit."""
+    from tmlibrary_amd import hip
+    bits = hip.OBJECT_SLOTS.bit_length() - 1
+    assert 1 << bits == hip.OBJECT_SLOTS
+    out, label = [], 0
+    while len(out) < count:
+        label += 1
+        if ((label * 2654435761) & 0xFFFFFFFF) >> (32 - bits) == bucket:
+            out.append(label)
+    return out
+
+
+def test_objects_probe_limit_in_a_nearly_empty_table(L):
+    """k_object_table's probe loop giving up (t == kObjProbe) with the table
+    almost empty: TMH_OBJECT_PROBE + 8 labels hash to entry 7 of one tile, the
+    first to arrive fill entries 7 .. 7 + TMH_OBJECT_PROBE - 1, and the other 8
+    find no entry although some 480 are free -- they go to memory, two runs
+    each (2 x 3 blocks: the second add meets the first's bounds, not the
+    initial ones)."""
+    from tmlibrary_amd import hip
+    labels = same_bucket_labels(7, hip.OBJECT_PROBE + 8)
+    if hip.OBJECT_SLOTS == 512:
+        assert labels[:5] == [267, 644, 1254, 1864, 2241]
+    plane = np.zeros((16, 512), np.int32)
+    for k, label in enumerate(labels):
+        r, c = 1 + 4 * (k // 12), 5 + 40 * (k % 12)
+        plane[r:r + 2, c:c + 3] = label
+    assert tile_label_counts(plane) == {(0, 0): len(labels) + 1}
+    got = check_tables(plane[None])
+    assert got[0]["n"][labels].tolist() == [6] * len(labels)
+    assert int(np.count_nonzero(got[0]["n"])) == len(labels) + 1
+
+
+def test_objects_one_label_per_pixel_outlines(L):
+    """The outlines start from the table rows the memory route wrote
+    (contour_kernels.hip reads each label's bbox from them): 8,192 one-pixel
+    objects, each the second fallback (no opening, one point), against the
+    plain-loop literal."""
+    import contours_literal as cl
+    from test_gpu_contours import assert_equal_literal
+    from tmlibrary_amd.image import object_contours
+    planes = one_label_per_pixel()
+    rows, objects, contours, points = object_contours(planes)
+    want = lit.object_rows(planes[0], 8192)
+    for name in lit.ROW_DTYPE.names:
+        assert np.array_equal(rows[0][name], want[name]), name
+    assert_equal_literal((objects, contours, points), cl.object_contours(planes))
+
+
 @pytest.mark.parametrize("bad,message", [(-1, "negative label"), (8, "above max_label")])
 def test_objects_reject_labels_out_of_range(L, torch_, bad, message):
     from tmlibrary_amd import hip

@@ -378,6 +378,11 @@ int tmh_correct_u16_device(tmh_corrector* c, const uint16_t* dev_in, uint16_t* d
   return guard([&] {
     TMH_CHECK(c && (dev_in && dev_out || n_sites == 0) && n_sites >= 0, TMH_EINVAL, "bad arguments");
     check_clip(clip_lo, clip_hi, 65535);
+    // the f64 fixup re-reads the input after the streaming kernel has stored
+    // the output: input and output must not overlap
+    TMH_CHECK(n_sites == 0 || dev_in + n_sites * c->npx <= dev_out ||
+                  dev_out + n_sites * c->npx <= dev_in,
+              TMH_EINVAL, "input and output sites must not overlap");
     hipStream_t s = pick(c->stream, stream);
     const FixList fl = corrector_fixlist(c, n_sites, s);
     corrector_forms(c, s);

@@ -95,6 +95,13 @@ static void correct_stack_u16_dev(tmh_corrector* c, const uint16_t* dev_in, uint
   const std::vector<int32_t> t = stack_table(c, dev_in, dev_out, n_planes, H, W, host_site,
                                              host_slot, host_windows, n_sites, slots, out_h, out_w);
   if (n_sites == 0 || out_h == 0 || out_w == 0) return;
+  // the f64 fixup re-reads the planes after the stack is stored (and the pass
+  // gathers from planes other workgroups may have written over): input and
+  // output must not overlap
+  const uint16_t* in_end = dev_in + n_planes * (int64_t)H * W;
+  const uint16_t* out_end = dev_out + n_sites * (int64_t)out_h * out_w * slots;
+  TMH_CHECK(n_planes == 0 || in_end <= dev_out || out_end <= dev_in, TMH_EINVAL,
+            "input and output of the stack must not overlap");
   hipStream_t s = pick(c ? c->stream : nullptr, stream);
   const int any_unmapped =
       std::count(t.begin(), t.begin() + n_sites * slots, (int32_t)-1) > 0 ? 1 : 0;

@@ -35,8 +35,8 @@
 namespace tmh {
 
 constexpr int kObjRows = 16, kObjCols = 512;  // a workgroup's tile
-constexpr int kObjSlots = 512;                // LDS table entries (22.5 KB)
-constexpr int kObjProbe = 16;
+constexpr int kObjSlots = TMH_OBJECT_SLOTS;   // LDS table entries (22.5 KB)
+constexpr int kObjProbe = TMH_OBJECT_PROBE;
 constexpr int kObjBatch = 4;                  // row segments loaded ahead per wave
 
 __global__ void k_label_minmax_init(int32_t* __restrict__ mx, int32_t* __restrict__ mn, int64_t n) {
@@ -196,6 +196,7 @@ __global__ __launch_bounds__(256) void k_object_table(const int32_t* __restrict_
 }
 
 static_assert(kObjSlots == 512, "the hash keeps 9 bits");
+static_assert(kObjProbe >= 1 && kObjProbe < kObjSlots, "a probe sequence stays inside the table");
 static_assert(sizeof(tmh_object_row) == 48, "tmh_object_row layout (include/tmhip.h)");
 
 void launch_label_minmax(const int32_t* planes, int64_t n_planes, int64_t npx, int32_t* d_max,

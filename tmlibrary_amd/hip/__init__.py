@@ -166,6 +166,10 @@ OBJECT_ROW_DTYPE = np.dtype([("n", np.int64), ("sum_y", np.int64), ("sum_x", np.
                              ("y0", np.int32), ("y1", np.int32), ("x0", np.int32),
                              ("x1", np.int32), ("border", np.int32), ("pad", np.int32)])
 assert OBJECT_ROW_DTYPE.itemsize == 48
+#: TMH_OBJECT_SLOTS / TMH_OBJECT_PROBE: the table kernel's LDS hash entries per tile and
+#: its probe limit; a label that finds no entry is added to its row in memory
+OBJECT_SLOTS = 512
+OBJECT_PROBE = 16
 
 
 #: struct tmh_contour (include/tmhip.h): one border of one object
