@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TMH_ABI_VERSION 8
+#define TMH_ABI_VERSION 9
 
 #define TMH_OK 0
 #define TMH_EINVAL (-22)  /* bad argument: maps to ValueError / TypeError */
@@ -884,6 +884,98 @@ int tmh_object_contours(const int32_t* host_planes, int64_t n_planes, int height
                         tmh_contour* host_contours, int64_t contour_capacity,
                         int32_t* host_points, int64_t point_capacity, int64_t* n_contours,
                         int64_t* n_points);
+
+/* ---- the clustering tool -------------------------------------------------
+ * tmlib/tools/clustering.py:40-99 through Classifier.train_unsupervised /
+ * predict (tmlib/tools/base.py:586-645): RobustScaler(quantile_range=(1, 99))
+ * and KMeans on a feature table.  x is row-major [n][d] f64 (DataFrame.values);
+ * all arithmetic is f64.  1 <= d <= TMH_CLUSTER_MAX_D, 1 <= k <=
+ * TMH_CLUSTER_MAX_K, k * d <= TMH_CLUSTER_MAX_KD (the centres fit in 64 KB of
+ * LDS), n < 2^31; anything larger is TMH_EINVAL.  Fit and seed pick k rows
+ * as centres and need k <= n; predict labels any number of rows.  center / scale [d]
+ * (both NULL: none) are applied as (x - center) / scale -- one subtract, one
+ * divide -- while a kernel loads x: the result is what the same call gives on
+ * the array tmh_robust_scale writes, bit for bit.  No sum is decided by a
+ * floating-point atomic: the same input gives the same bytes on every run.
+ * Every call returns when its host outputs are filled; `stream` (NULL: the
+ * default stream) carries the work.  The _device forms take x (and center,
+ * scale, labels, min_dist, out) in device memory, the host forms in host
+ * memory; small tables (ranks, draws, centres, counts) are host memory in both. */
+#define TMH_CLUSTER_MAX_D 256
+#define TMH_CLUSTER_MAX_K 64
+#define TMH_CLUSTER_MAX_KD 8192
+#define TMH_CLUSTER_MAX_RANKS 64
+#define TMH_CLUSTER_MAX_TRIALS 16
+/* Per column: host_count = values that are not NaN, host_inf = values that are
+ * +-inf; host_mean / host_var (each may be NULL) = mean and variance of the
+ * scaled column over its non-NaN values, np.var's definition (two passes,
+ * divisor = the count), summed in a fixed order. */
+int tmh_column_census_device(const double* dev_x, int64_t n, int d, const double* dev_center,
+                             const double* dev_scale, int64_t* host_count, int64_t* host_inf,
+                             double* host_mean, double* host_var, void* stream);
+int tmh_column_census(const double* host_x, int64_t n, int d, const double* host_center,
+                      const double* host_scale, int64_t* host_count, int64_t* host_inf,
+                      double* host_mean, double* host_var);
+/* host_values[f][q] = the value at 0-based rank host_ranks[f][q] among column
+ * f's non-NaN values in ascending order, exactly (a radix select on the
+ * order-preserving 64-bit image of the f64; -0.0 sorts below +0.0, the two are
+ * equal as values).  1 <= r <= TMH_CLUSTER_MAX_RANKS; a rank outside the
+ * column's non-NaN count: TMH_EINVAL.  host_count [d]: the non-NaN counts
+ * tmh_column_census returned for the same x, against which the ranks are
+ * checked (with a count above the column's true one, a rank past the true
+ * count returns NaN; nothing is read out of bounds); NULL: the call takes a
+ * census of its own, one more read of x. */
+int tmh_column_select_device(const double* dev_x, int64_t n, int d, const int64_t* host_count,
+                             const int64_t* host_ranks, int r, double* host_values, void* stream);
+int tmh_column_select(const double* host_x, int64_t n, int d, const int64_t* host_count,
+                      const int64_t* host_ranks, int r, double* host_values);
+/* out = (x - center) / scale (RobustScaler.transform); x and out must not overlap. */
+int tmh_robust_scale_device(const double* dev_x, int64_t n, int d, const double* dev_center,
+                            const double* dev_scale, double* dev_out, void* stream);
+int tmh_robust_scale(const double* host_x, int64_t n, int d, const double* host_center,
+                     const double* host_scale, double* host_out);
+/* k-means++ as scikit-learn's _kmeans_plusplus states it.  `first` is the
+ * first centre's row; host_draws [k - 1][trials] are the uniform draws of each
+ * step (trials = 2 + int(log(k)) for scikit-learn's choice, at most
+ * TMH_CLUSTER_MAX_TRIALS).  Per step: target = draw * current potential; the
+ * candidate is the first row whose inclusive prefix sum of the closest squared
+ * distances reaches the target (at most n - 1); the trial with the smallest
+ * potential is kept (the first of equals).  host_indices [k], host_centers
+ * [k][d] (scaled).  host_trace (may be NULL) [k - 1][3 * trials + 1] doubles:
+ * per step the targets, the candidate rows, the potentials, the kept trial.
+ * The k-means calls return TMH_EINVAL when x holds NaN or +-inf. */
+int tmh_kmeans_seed_device(const double* dev_x, int64_t n, int d, int k, const double* dev_center,
+                           const double* dev_scale, int64_t first, const double* host_draws,
+                           int trials, int32_t* host_indices, double* host_centers,
+                           double* host_trace, void* stream);
+int tmh_kmeans_seed(const double* host_x, int64_t n, int d, int k, const double* host_center,
+                    const double* host_scale, int64_t first, const double* host_draws, int trials,
+                    int32_t* host_indices, double* host_centers, double* host_trace);
+/* labels[i] = argmin_j sum_f (x_if - c_jf)^2, summed in feature order, the
+ * first minimum; min_dist (may be NULL) [n] = that minimum.  x must not
+ * overlap labels or min_dist. */
+int tmh_kmeans_predict_device(const double* dev_x, int64_t n, int d, int k, const double* dev_center,
+                              const double* dev_scale, const double* host_centers,
+                              int32_t* dev_labels, double* dev_min_dist, void* stream);
+int tmh_kmeans_predict(const double* host_x, int64_t n, int d, int k, const double* host_center,
+                       const double* host_scale, const double* host_centers, int32_t* host_labels,
+                       double* host_min_dist);
+/* Lloyd's iterations from host_init [k][d] as scikit-learn's
+ * _kmeans_single_lloyd runs them.  *tol_abs = tol * the mean of the scaled
+ * columns' variances.  An iteration assigns, then moves the centres; an empty
+ * cluster (ascending index) takes the row farthest from its own centre (ties:
+ * the lowest row; rows in descending distance), which leaves its old cluster.
+ * The loop stops when no label changed or when the summed squared centre shift
+ * is <= *tol_abs; unless it stopped on unchanged labels one more assign makes
+ * the labels those of the final centres.  *n_iter counts as n_iter_ does. */
+int tmh_kmeans_fit_device(const double* dev_x, int64_t n, int d, int k, const double* dev_center,
+                          const double* dev_scale, const double* host_init, int max_iter, double tol,
+                          double* host_centers, int32_t* dev_labels, double* inertia, int* n_iter,
+                          double* tol_abs, void* stream);
+int tmh_kmeans_fit(const double* host_x, int64_t n, int d, int k, const double* host_center,
+                   const double* host_scale, const double* host_init, int max_iter, double tol,
+                   double* host_centers, int32_t* host_labels, double* inertia, int* n_iter,
+                   double* tol_abs);
 
 /* ---- device memory helpers for callers without another allocator -------- */
 int tmh_malloc_device(void** dev_ptr, size_t bytes);

@@ -481,6 +481,47 @@ void contours_write(const int32_t* planes, int H, int W, int32_t max_label,
                     const tmh_object_row* rows, tmh_contour_object* objects,
                     const ContourScratch& scratch, tmh_contour* contours, int32_t* points,
                     hipStream_t s);
+// the clustering tool (cluster_kernels.hip): X is [n][d] f64; cen / scl
+// (nullptr: none) are applied as (x - c) / s on load.  cnt[2 d]: per column the
+// non-NaN values, then the +-inf values.  The *_chunks functions size the
+// partial buffers of the fixed-order sums.
+void cluster_census(const double* X, int64_t n, int d, unsigned long long* cnt, hipStream_t s);
+int64_t cluster_colsum_chunks(int64_t n);
+// out[f] = sum of x (mean == nullptr) or of (x - mean[f])^2 over the column's non-NaN rows / cnt[f]
+void cluster_colstat(const double* X, int64_t n, int d, const double* cen, const double* scl,
+                     const unsigned long long* cnt, const double* mean, double* part, double* out,
+                     hipStream_t s);
+int64_t cluster_sum_chunks(int64_t n);
+// out[v] = the sum of vec[v][0..n), v < n_vec; part[n_vec * chunks]
+void cluster_sum(const double* vec, int64_t n, int n_vec, double* part, double* out, hipStream_t s);
+void cluster_robust_scale(const double* X, int64_t n, int d, const double* cen, const double* scl,
+                          double* out, hipStream_t s);
+// state[d * r][2] = (0, rank); hist[d * r * 256]; out[d * r]
+void cluster_select(const double* X, int64_t n, int d, int r, unsigned long long* state,
+                    unsigned int* hist, double* out, hipStream_t s);
+int64_t cluster_assign_chunks(int64_t n, int d, int k);
+// psums[chunks][k][d] / pcounts[chunks][k] (both nullptr: labels only); prev
+// and changed are given together or not at all
+void cluster_assign(const double* X, int64_t n, int d, int k, const double* cen, const double* scl,
+                    const double* centres, const int32_t* prev, int32_t* labels, double* mind,
+                    int* changed, double* psums, unsigned int* pcounts, hipStream_t s);
+// taken[k]: scratch of the empty-cluster rule
+void cluster_update(const double* X, int64_t n, int d, int k, const double* cen, const double* scl,
+                    const int32_t* labels, const double* mind, const double* psums,
+                    const unsigned int* pcounts, double* sums, long long* counts, const double* old,
+                    double* centres_new, double* shift, int64_t* taken, hipStream_t s);
+int64_t cluster_seed_blocks(int64_t n);
+void cluster_seed_trials(const double* X, int64_t n, int d, int trials, const double* cen,
+                         const double* scl, const int64_t* cand, const double* closest, double* out,
+                         hipStream_t s);
+void cluster_seed_search(const double* closest, int64_t n, int trials, const double* draws,
+                         const double* pot, double* block_tot, double* block_excl, double* targets,
+                         int64_t* cand, hipStream_t s);
+void cluster_seed_pick(const double* pots, int trials, const int64_t* cand, const double* targets,
+                       int step, double* pot, int* best, int32_t* indices, double* trace, int tmax,
+                       const double* trial_closest, int64_t n, double* closest, hipStream_t s);
+void cluster_gather_rows(const double* X, int d, int k, const double* cen, const double* scl,
+                         const int32_t* indices, double* centres, hipStream_t s);
 // site-image input (inflate_kernels.hip)
 int64_t inflate_scratch_bytes(int64_t n_chunks, int64_t raw_max);
 void launch_inflate(const uint8_t* src, int64_t src_bytes, const tmh_zchunk* chunks,

@@ -33,7 +33,7 @@ TMH_FUSED_NO_HIST = 100
 TMH_SYNTH_STANDARD = 0
 TMH_SYNTH_BRIGHT = 1
 TMH_SYNTH_UNIFORM = 2
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _P = C.c_void_p
 _I64 = C.c_int64
@@ -141,6 +141,20 @@ SIGNATURES = {
                                         C.POINTER(_I64), C.POINTER(_I64), _P]),
     "tmh_object_contours": (_I, [_P, _I64, _I, _I, C.POINTER(C.c_int32), _P, _P, _I64, _P, _I64, _P,
                                  _I64, C.POINTER(_I64), C.POINTER(_I64)]),
+    "tmh_column_census_device": (_I, [_P, _I64, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "tmh_column_census": (_I, [_P, _I64, _I, _P, _P, _P, _P, _P, _P]),
+    "tmh_column_select_device": (_I, [_P, _I64, _I, _P, _P, _I, _P, _P]),
+    "tmh_column_select": (_I, [_P, _I64, _I, _P, _P, _I, _P]),
+    "tmh_robust_scale_device": (_I, [_P, _I64, _I, _P, _P, _P, _P]),
+    "tmh_robust_scale": (_I, [_P, _I64, _I, _P, _P, _P]),
+    "tmh_kmeans_seed_device": (_I, [_P, _I64, _I, _I, _P, _P, _I64, _P, _I, _P, _P, _P, _P]),
+    "tmh_kmeans_seed": (_I, [_P, _I64, _I, _I, _P, _P, _I64, _P, _I, _P, _P, _P]),
+    "tmh_kmeans_predict_device": (_I, [_P, _I64, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "tmh_kmeans_predict": (_I, [_P, _I64, _I, _I, _P, _P, _P, _P, _P]),
+    "tmh_kmeans_fit_device": (_I, [_P, _I64, _I, _I, _P, _P, _P, _I, _D, _P, _P, C.POINTER(_D),
+                                   C.POINTER(_I), C.POINTER(_D), _P]),
+    "tmh_kmeans_fit": (_I, [_P, _I64, _I, _I, _P, _P, _P, _I, _D, _P, _P, C.POINTER(_D),
+                            C.POINTER(_I), C.POINTER(_D)]),
     "tmh_malloc_device": (_I, [C.POINTER(_P), C.c_size_t]),
     "tmh_free_device": (_I, [_P]),
     "tmh_memcpy": (_I, [_P, _P, C.c_size_t, _I, _P]),

@@ -46,3 +46,15 @@ def stats_log10_lut() -> np.ndarray:
         lut = np.log10(x)
     lut[0] = 0.0
     return np.ascontiguousarray(lut)
+
+
+def lerp(a, b, gamma):
+    """numpy's ``_lerp`` on f64 order statistics: ``a + (b - a) * gamma``, or
+    ``b - (b - a) * (1 - gamma)`` where ``gamma >= 0.5`` (no fused multiply-add)."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    gamma = np.asarray(gamma, dtype=np.float64)
+    diff = b - a
+    out = np.asarray(a + diff * gamma)
+    np.subtract(b, diff * (1 - gamma), out=out, where=gamma >= 0.5)
+    return out
