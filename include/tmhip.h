@@ -691,7 +691,11 @@ typedef struct tmh_zchunk {
 #define TMH_Z_ADLER 7      /* Adler-32 mismatch */
 #define TMH_Z_SIZE 8       /* fewer than raw_len bytes */
 #define TMH_Z_STORED 9     /* stored block LEN / NLEN mismatch */
-#define TMH_Z_TABLE 10     /* invalid code lengths (over-subscribed, no end code) */
+/* TMH_Z_TABLE also covers the incomplete codes zlib's inflate_table rejects:
+ * a code that leaves bit patterns unused is taken only as exactly one code of
+ * length 1 (for distances also as no code at all), never for the code-length
+ * code. */
+#define TMH_Z_TABLE 10     /* invalid code lengths (over-subscribed, incomplete, no end code) */
 /* Two kernels: each lane Huffman-decodes one chunk, writing its literal bytes
  * and listing its back-references in dev_scratch (no lane waits on a load of
  * earlier output); then one wave per chunk resolves the list in order, 64

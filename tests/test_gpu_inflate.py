@@ -10,6 +10,14 @@ per chunk (TMH_Z_*) without touching other chunks.  Then whole channel image
 files: DeviceChunkDecoder on files written through libtmh5 (whole-row and
 2-D chunks with edge padding, uint8 and uint16, several levels) equals the
 host read (libhdf5 + zlib), and at full size (2160x2560 synthetic sites).
+
+The hand-built streams of tests/inflate_cases.py -- what the format allows and
+zlib's encoder never emits, the dependency patterns of the match resolver
+(k_resolve_matches has no host twin), one stream per status clause, every
+bit flip and truncation of four seeds, odd layouts -- run through the device
+at every workgroup width; tests/test_inflate_host.py runs the same cases
+through the host build of the core under the sanitizers.  tmh_place_chunks_device
+is checked alone against numpy slice assignment.
 """
 import ctypes as C
 import os
@@ -17,6 +25,8 @@ import zlib
 
 import numpy as np
 import pytest
+
+import inflate_cases as ic
 
 pytestmark = pytest.mark.gpu
 
@@ -233,3 +243,163 @@ def test_corrupt_file_raises(L, tmp_path):
     dec.decode(paths, out.data_ptr())
     with pytest.raises(IOError, match="channel_image_file_1.h5: chunk 6"):
         dec.check()
+
+
+# ---- the hand-built families (tests/inflate_cases.py)
+
+class _Device:
+    """Launches of tmh_inflate_device on device buffers that only grow."""
+
+    def __init__(self, L):
+        self.L, self.bufs = L, {}
+
+    def buf(self, key, nbytes):
+        from test_gpu_parity import Dev
+        b = self.bufs.get(key)
+        if b is None or b.nbytes < nbytes:
+            if b is not None:
+                b.free()
+            b = self.bufs[key] = Dev(self.L, max(nbytes, 1) * 2)
+        return b
+
+    def run(self, blob, rows, raw_bytes):
+        """The whole raw buffer (pre-filled with the sentinel) and the statuses."""
+        from tmlibrary_amd import hip
+        from test_inflate_host import table_of
+        L, n = self.L, len(rows)
+        tab = table_of(rows)
+        raw_max = int(tab["raw_len"].max())
+        scr = int(L.tmh_inflate_scratch_bytes(n, raw_max))
+        d_src, d_tab = self.buf("src", len(blob)), self.buf("tab", tab.nbytes)
+        d_raw, d_st, d_scr = self.buf("raw", raw_bytes), self.buf("st", 4 * n), self.buf("scr", scr)
+        if blob:
+            d_src.put(np.frombuffer(blob, np.uint8))
+        d_tab.put(tab)
+        d_raw.put(np.full(max(raw_bytes, 1), ic.SENTINEL, np.uint8))
+        d_st.put(np.full(n, 0x7F7F7F7F, np.int32))
+        hip.check(L.tmh_inflate_device(d_src.p, len(blob), d_tab.p, n, raw_max, d_raw.p, raw_bytes,
+                                       d_scr.p, scr, d_st.p, None))
+        assert L.tmh_synchronize(None) == 0
+        return d_raw.get(np.uint8, (max(raw_bytes, 1),))[:raw_bytes], d_st.get(np.int32, (n,))
+
+    def free(self):
+        for b in self.bufs.values():
+            b.free()
+
+
+@pytest.fixture(scope="module")
+def dev(L):
+    d = _Device(L)
+    yield d
+    d.free()
+
+
+@pytest.fixture(scope="module")
+def host_exe(tmp_path_factory):
+    from test_inflate_host import build_harness
+    return build_harness(tmp_path_factory.mktemp("inflate_host"), False)
+
+
+def _check_launches(dev, named):
+    for name, cases, kw in named:
+        blob, rows, raw_bytes = ic.layout(cases, **kw)
+        raw, st = dev.run(blob, rows, raw_bytes)
+        ic.check_outputs(cases, rows, raw, st, name)
+
+
+@pytest.mark.parametrize("family", ["A", "B", "C"])
+@pytest.mark.parametrize("lanes", [None, 4, 64])
+def test_hand_built_family_on_device(dev, monkeypatch, lanes, family):
+    """A: distance 32768, every length and distance symbol at both ends of its
+    extra bits, codes of 1..15 bits, repeat codes across the literal/distance
+    boundary, the incomplete codes zlib allows, empty and stored blocks.
+    B: every length 3..258 at the distances where the resolver's copy changes
+    form, 300 token streams whose matches' sources end at, one byte inside, or
+    63/64 matches behind an earlier destination, and the longest match lists
+    (each also launched alone: raw_max its own raw_len).  C: the exact status
+    of every clause, nothing written past the fault.  Bytes no chunk owns
+    keep the sentinel."""
+    if lanes:
+        monkeypatch.setenv("TMH_INFLATE_LANES", str(lanes))
+    cases = ic.families()[family]
+    named = [(family, cases, {})]
+    named += [(c.name, [c], {}) for c in cases if c.name.startswith("cap_")]
+    _check_launches(dev, named)
+
+
+@pytest.mark.parametrize("lanes", [None, 4, 64])
+def test_layouts_on_device(dev, monkeypatch, lanes):
+    """One stream at source offsets 0..39 x output offsets 0/1/5/15 x 0/1/15/16/17
+    bytes behind it in the buffer; launches of 1, W - 1, W, W + 1 streams;
+    failing, short and long streams mixed in the workgroups; stored
+    (TMH_ZCHUNK_STORED) chunks at odd offsets between deflated ones."""
+    if lanes:
+        monkeypatch.setenv("TMH_INFLATE_LANES", str(lanes))
+    _check_launches(dev, ic.family_e())
+
+
+def test_invalid_streams_device_equals_host_core(dev, host_exe, tmp_path):
+    """Families C and D (every bit flip and truncation, none left out): the
+    outcome zlib dictates, and beyond it the device's status and every byte
+    of the raw buffer -- what a failing chunk wrote before its fault
+    included -- equal the host build of the same core."""
+    from test_inflate_host import run_batch
+    fam = ic.families()
+    groups = [fam["C"]] + ic.split_launches(fam["D"])
+    lay = [ic.layout(g) for g in groups]
+    host = run_batch(host_exe, tmp_path, lay)
+    for i, (g, (blob, rows, raw_bytes), (h_raw, h_st)) in enumerate(zip(groups, lay, host)):
+        raw, st = dev.run(blob, rows, raw_bytes)
+        ic.check_outputs(g, rows, raw, st, "launch %d" % i)
+        diff = [(c.name, int(a), int(b)) for c, a, b in zip(g, st, h_st) if a != b]
+        assert not diff, "(name, device, host): %s" % diff[:20]
+        assert np.array_equal(raw, h_raw), "launch %d: raw bytes differ from the host core's" % i
+
+
+@pytest.mark.parametrize("H,W,dtype,cr,cc,shift", [
+    (40, 72, np.uint16, 16, 32, 0),   # 16-byte path; right-edge chunks place 8 columns, bottom clipped
+    (40, 72, np.uint16, 16, 32, 2),   # the same from raw offsets that are not 16-byte aligned
+    (33, 70, np.uint16, 16, 32, 0),   # row stride 140 bytes: the byte path, both edges clipped
+    (48, 80, np.uint8, 16, 16, 0),
+    (17, 20, np.uint32, 8, 8, 0),
+    (16, 32, np.uint16, 16, 32, 0),   # one chunk per image
+])
+def test_place_chunks_against_slice_assignment(L, H, W, dtype, cr, cc, shift):
+    """tmh_place_chunks_device on a raw buffer of known bytes equals numpy
+    slice assignment; a chunk left out of the table leaves its pixels alone,
+    and so does the border around the images."""
+    from tmlibrary_amd import hip
+    from test_gpu_parity import Dev
+    rng = np.random.default_rng(H * W + shift)
+    es, n_img, border = np.dtype(dtype).itemsize, 3, 64
+    grid = [(i, r, c) for i in range(n_img) for r in range(0, H, cr) for c in range(0, W, cc)]
+    order = rng.permutation(len(grid))  # raw order is not image order
+    chunks = rng.integers(0, 256, (len(grid), cr * cc * es), dtype=np.uint8)
+    chunks[chunks == ic.SENTINEL] = 0
+    tab = np.zeros(len(grid), hip.ZCHUNK_DTYPE)
+    raw = np.full(shift + chunks.size + 16, 0x11, np.uint8)
+    want = np.full((n_img, H, W * es), ic.SENTINEL, np.uint8)
+    skipped = len(grid) // 2 if len(grid) > n_img else -1
+    for k, g in enumerate(order):
+        i, r, c = grid[g]
+        off = shift + k * chunks.shape[1]
+        raw[off:off + chunks.shape[1]] = chunks[g]
+        tab[g] = (0, 0, off, chunks.shape[1], i, r, c, 0, 0)
+        if g != skipped:
+            rows, cols = min(cr, H - r), min(cc, W - c)
+            want[i, r:r + rows, c * es:(c + cols) * es] = chunks[g].reshape(cr, cc * es)[:rows, :cols * es]
+    tab = np.delete(tab, skipped) if skipped >= 0 else tab
+    d_raw, d_tab, d_img = Dev(L, raw.nbytes), Dev(L, tab.nbytes), Dev(L, want.size + 2 * border)
+    d_raw.put(raw)
+    d_tab.put(tab)
+    d_img.put(np.full(want.size + 2 * border, ic.SENTINEL, np.uint8))
+    hip.check(L.tmh_place_chunks_device(d_raw.p, d_tab.p, len(tab), H, W, es, cr, cc,
+                                        C.c_void_p(d_img.p.value + border), None))
+    assert L.tmh_synchronize(None) == 0
+    got = d_img.get(np.uint8, (want.size + 2 * border,))
+    for b in (d_raw, d_tab, d_img):
+        b.free()
+    assert np.all(got[:border] == ic.SENTINEL) and np.all(got[-border:] == ic.SENTINEL)
+    assert np.array_equal(got[border:-border].reshape(want.shape), want)
+    if skipped >= 0:
+        assert np.any(want == ic.SENTINEL)

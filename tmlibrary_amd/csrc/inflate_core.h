@@ -273,10 +273,18 @@ TMH_ZDEV int hdecode(Bits& b, const uint8_t* src, ZShared<W>& z, uint16_t (*fast
   return sym[i < (uint32_t)nsym ? i : (uint32_t)nsym - 1u][lane];
 }
 
+// Which code hbuild builds: what zlib's inflate_table takes for an incomplete
+// code depends on it (below).
+enum : int { kCodeLens = 0, kCodeLitLen = 1, kCodeDist = 2 };
+
 // Canonical tables from n code lengths (lens column of this lane, or the
 // fixed code), with the first-level table of the codes of at most FB bits;
-// returns false for an over-subscribed code.
-template <int FB, int W>
+// returns false for an over-subscribed code, and for an incomplete one that
+// zlib's inflate_table rejects: a code that leaves bit patterns unused is
+// allowed only as exactly one code of length 1 (literal/length and distance
+// codes), or as no code at all (distance codes); the code-length code must be
+// complete.  Once per block header: the data loop never sees the rule.
+template <int FB, int W, int Kind>
 TMH_ZDEV bool hbuild(ZShared<W>& z, int lane, const uint8_t (*lens)[W], int off, int n,
                      uint16_t (*fast)[W], uint16_t (*lim)[W], uint16_t (*base)[W],
                      uint16_t (*sym)[W]) {
@@ -287,8 +295,10 @@ TMH_ZDEV bool hbuild(ZShared<W>& z, int lane, const uint8_t (*lens)[W], int off,
     if (l) z.tmp[l][lane] += 1;
   }
   uint32_t code = 0, offs = 0;
+  bool one = false;  // exactly one code of length 1
   for (int l = 1; l < 16; ++l) {
     const uint32_t cnt = z.tmp[l][lane];
+    if (l == 1) one = cnt == 1;
     base[l][lane] = (uint16_t)(offs - code);
     code += cnt;
     if (code > (1u << l)) return false;
@@ -297,6 +307,10 @@ TMH_ZDEV bool hbuild(ZShared<W>& z, int lane, const uint8_t (*lens)[W], int off,
     offs += cnt;
     code <<= 1;
   }
+  // code = the codes' share of the 2^16 patterns of 16 bits; offs = the codes
+  if (code != (1u << 16) &&
+      (Kind == kCodeLens || !((offs == 1 && one) || (Kind == kCodeDist && offs == 0))))
+    return false;
   for (int s = 0; s < n; ++s) {
     const int l = lens[off + s][lane];
     if (l) {
@@ -384,9 +398,12 @@ TMH_ZDEV int inflate_tokens(const uint8_t* __restrict__ src, int64_t src_bytes,
     b.nb = 32 - sh;
   }
   const int64_t in_bits = (int64_t)c.src_len * 8;
-  // loads running this far past the stream mean a corrupt stream (checked per
-  // symbol on the ring's load position; exactly at the trailer)
-  const int64_t p_limit = c.src_off + c.src_len + 256;
+  // taking dwords this far past the stream means a corrupt stream (checked per
+  // symbol; exactly at the trailer).  On the dwords the lane has taken, not on
+  // the ring's load position: the ring is topped up when any lane of the wave
+  // runs low, and a chunk's status must not depend on its neighbours.
+  const int64_t head_end = ((c.src_off & 15) + c.src_len + 256) >> 2;
+  const uint32_t head_limit = head_end < 0xFFFFFFFFll ? (uint32_t)head_end : 0xFFFFFFFFu;
   // zlib header (RFC 1950): CM = 8, CINFO <= 7, FCHECK, no preset dictionary
   const uint32_t cmf = getb<W>(b, src, z, lane, 8), flg = getb<W>(b, src, z, lane, 8);
   if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u))
@@ -408,7 +425,10 @@ TMH_ZDEV int inflate_tokens(const uint8_t* __restrict__ src, int64_t src_bytes,
     const uint64_t t0 = TMH_ZCLOCK();
     const int st0 = state;
 #endif
-    if (consumed_bits(b, c.src_off) > in_bits + 64) {  // ran far past the stream: corrupt
+    // ran far past the stream: corrupt (between a lane's own header steps: the
+    // wave leaves the data loop whenever any lane does, so a check here on a
+    // lane still in its block would make its status depend on the others)
+    if (state != kStData && consumed_bits(b, c.src_off) > in_bits + 64) {
       err = kZInput;
       break;
     }
@@ -452,7 +472,7 @@ TMH_ZDEV int inflate_tokens(const uint8_t* __restrict__ src, int64_t src_bytes,
             o += len;
           }
         }
-        if (b.p > p_limit) ecode = kZInput;  // ran far past the stream: corrupt
+        if (b.head > head_limit) ecode = kZInput;  // ran far past the stream: corrupt
         if (ecode) {
           err = ecode;
           state = kStDone;
@@ -484,8 +504,10 @@ TMH_ZDEV int inflate_tokens(const uint8_t* __restrict__ src, int64_t src_bytes,
         for (int s = 0; s < 288; ++s)
           z.lens[s][lane] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8);
         for (int s = 0; s < 32; ++s) z.lens[288 + s][lane] = 5;
-        if (!hbuild<kLFast, W>(z, lane, z.lens, 0, 288, z.lfast, z.llim, z.lbase, z.lsym) ||
-            !hbuild<kDFast, W>(z, lane, z.lens, 288, 32, z.dfast, z.dlim, z.dbase, z.dsym)) {
+        if (!hbuild<kLFast, W, kCodeLitLen>(z, lane, z.lens, 0, 288, z.lfast, z.llim, z.lbase,
+                                            z.lsym) ||
+            !hbuild<kDFast, W, kCodeDist>(z, lane, z.lens, 288, 32, z.dfast, z.dlim, z.dbase,
+                                          z.dsym)) {
           err = kZTable;
           break;
         }
@@ -500,7 +522,8 @@ TMH_ZDEV int inflate_tokens(const uint8_t* __restrict__ src, int64_t src_bytes,
         for (int i = 0; i < 19; ++i) z.lens[i][lane] = 0;
         for (int i = 0; i < hclen; ++i) z.lens[kClOrder[i]][lane] = (uint8_t)getb<W>(b, src, z, lane, 3);
         // the code-length code lives in the distance tables until the real ones are built
-        if (!hbuild<kDFast, W>(z, lane, z.lens, 0, 19, z.dfast, z.dlim, z.dbase, z.dsym)) {
+        if (!hbuild<kDFast, W, kCodeLens>(z, lane, z.lens, 0, 19, z.dfast, z.dlim, z.dbase,
+                                          z.dsym)) {
           err = kZTable;
           break;
         }
@@ -536,8 +559,10 @@ TMH_ZDEV int inflate_tokens(const uint8_t* __restrict__ src, int64_t src_bytes,
         }
         if (err) break;
         if (z.lens[256][lane] == 0 ||  // no end-of-block code
-            !hbuild<kLFast, W>(z, lane, z.lens, 0, hlit, z.lfast, z.llim, z.lbase, z.lsym) ||
-            !hbuild<kDFast, W>(z, lane, z.lens, hlit, hdist, z.dfast, z.dlim, z.dbase, z.dsym)) {
+            !hbuild<kLFast, W, kCodeLitLen>(z, lane, z.lens, 0, hlit, z.lfast, z.llim, z.lbase,
+                                            z.lsym) ||
+            !hbuild<kDFast, W, kCodeDist>(z, lane, z.lens, hlit, hdist, z.dfast, z.dlim, z.dbase,
+                                          z.dsym)) {
           err = kZTable;
           break;
         }
