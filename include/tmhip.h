@@ -981,6 +981,99 @@ int tmh_kmeans_fit(const double* host_x, int64_t n, int d, int k, const double* 
                    double* host_centers, int32_t* host_labels, double* inertia, int* n_iter,
                    double* tol_abs);
 
+/* ---- the supervised classification tool ------------------------------------
+ * tmlib/tools/classification.py:45-116 through Classifier.predict
+ * (tmlib/tools/base.py:621-645): the labels scikit-learn's
+ * RandomForestClassifier.predict and SVC.predict give, from a flat model that
+ * the Python layer exports from the fitted estimator.  Training is not here.
+ * x is row-major [n][d] f64, 1 <= d <= TMH_CLUSTER_MAX_D, n < 2^31; x holding
+ * NaN or +-inf is TMH_EINVAL.  The _device forms take x (and center, scale,
+ * labels, proba, dec) in device memory, the host forms in host memory; the
+ * model arrays of the create calls are host memory.  Every predict returns
+ * when its work is done; x must not overlap an output, nor labels the other
+ * output (TMH_EINVAL).
+ *
+ * Forest (RandomForestClassifier.predict of scikit-learn 1.7.2).  x is cast to
+ * float32, round to nearest even; a finite value whose cast is infinite is
+ * TMH_EINVAL.  At a node the row goes left iff (double)x_f32[feature] <=
+ * threshold.  A leaf contributes its row of leaf_value (fractions, not
+ * renormalised).  The trees' rows are added in f64 in tree order into zero,
+ * each class sum is divided by n_trees once, the label is the first maximum:
+ * labels and proba [n][n_classes] (may be NULL) equal scikit-learn's exactly.
+ *
+ * The model: feature [nodes] (-1: a leaf), threshold [nodes], left / right
+ * [nodes], leaf_row [nodes] (a leaf's row of leaf_value), tree_root [n_trees]
+ * (ascending from 0; a tree owns the nodes from its root up to the next
+ * tree's), leaf_value [n_leaves][n_classes].  2 <= n_classes <=
+ * TMH_FOREST_MAX_CLASSES, 1 <= n_trees <= TMH_FOREST_MAX_TREES, nodes <
+ * TMH_FOREST_MAX_NODES.  tmh_forest_create checks before anything is
+ * uploaded, TMH_EINVAL otherwise: an internal node's children lie inside its
+ * tree and have indices greater than its own (so every walk ends), no node is
+ * reached twice, feature < d, no threshold is NaN, every leaf_row is in range,
+ * the leaf values are finite.
+ *
+ * Two routes, chosen by the model alone (tmh_forest_route): packed nodes
+ * (16 bytes each, the nodes a root reaches) that fit 96 KB are staged into
+ * LDS once per workgroup (TMH_FOREST_ROUTE_LDS), a larger forest is walked in
+ * memory (TMH_FOREST_ROUTE_MEMORY).  TMH_OPT_FOREST_MEMORY_ROUTE = 1 forces
+ * the memory route.  Both give the same bytes. */
+#define TMH_FOREST_MAX_CLASSES 64
+#define TMH_FOREST_MAX_TREES 256
+#define TMH_FOREST_MAX_NODES (1 << 24)
+#define TMH_FOREST_ROUTE_LDS 0
+#define TMH_FOREST_ROUTE_MEMORY 1
+#define TMH_OPT_FOREST_MEMORY_ROUTE 20
+typedef struct tmh_forest tmh_forest;
+int tmh_forest_create(const int32_t* feature, const double* threshold, const int32_t* left,
+                      const int32_t* right, const int32_t* leaf_row, int64_t nodes,
+                      const int32_t* tree_root, int n_trees, const double* leaf_value,
+                      int64_t n_leaves, int n_classes, int d, tmh_forest** out);
+void tmh_forest_destroy(tmh_forest* h);
+int tmh_forest_set_option(tmh_forest* h, int option, int value);
+/* *route = the route a predict takes now; *packed_nodes (may be NULL) */
+int tmh_forest_route(const tmh_forest* h, int* route, int64_t* packed_nodes);
+int tmh_forest_predict_device(tmh_forest* h, const double* dev_x, int64_t n, int32_t* dev_labels,
+                              double* dev_proba, void* stream);
+int tmh_forest_predict(tmh_forest* h, const double* host_x, int64_t n, int32_t* host_labels,
+                       double* host_proba);
+/* SVC (libsvm's dense svm_predict_values as scikit-learn 1.7.2 ships it).
+ * center / scale [d] (both NULL: none) are applied as (x - center) / scale on
+ * load, as the clustering calls do.  K_s = exp(-gamma sum_f (x_f - sv_sf)^2)
+ * (TMH_SVC_RBF, the differenced form) or x . sv_s (TMH_SVC_LINEAR).  For each
+ * class pair (i < j) in libsvm's order (0,1), (0,2), ..., (1,2), ...:
+ *   dec = sum over the SVs of i of coef[j - 1][s] K_s
+ *       + sum over the SVs of j of coef[i][s] K_s - rho[p];
+ * the vote goes to i iff dec > 0, else to j; the label is the class with the
+ * most votes, the first on equality.  All arithmetic is f64; the sums run in
+ * ascending s as fused multiply-adds (libsvm's go through BLAS, whose order is
+ * free), so dec agrees with libsvm's within rounding, not bit for bit.  dec
+ * [n][k (k - 1) / 2] may be NULL.  A linear model is collapsed at create to
+ * one weight vector per pair.
+ *
+ * The model, in libsvm's own sign convention (scikit-learn's _dual_coef_ and
+ * -_intercept_, not the public attributes): sv [m][d] grouped by class, n_sv
+ * [k] adding up to m, coef [k - 1][m], rho [k (k - 1) / 2]; gamma > 0 for rbf.
+ * 2 <= k <= TMH_SVC_MAX_CLASSES, 1 <= m <= TMH_SVC_MAX_SV; every value
+ * finite; anything else is TMH_EINVAL.  The support vectors stream through LDS
+ * in tiles (tmh_svc_tile: SVs per tile, number of tiles); TMH_OPT_SVC_TILE
+ * caps the tile (0: no cap).  Every tile size gives the same bytes. */
+#define TMH_SVC_RBF 0
+#define TMH_SVC_LINEAR 1
+#define TMH_SVC_MAX_CLASSES 16
+#define TMH_SVC_MAX_SV 65536
+#define TMH_OPT_SVC_TILE 21
+typedef struct tmh_svc tmh_svc;
+int tmh_svc_create(int kernel, double gamma, const double* sv, int64_t m, int d, const int32_t* n_sv,
+                   int k, const double* coef, const double* rho, tmh_svc** out);
+void tmh_svc_destroy(tmh_svc* h);
+int tmh_svc_set_option(tmh_svc* h, int option, int value);
+int tmh_svc_tile(const tmh_svc* h, int* tile, int* n_tiles);
+int tmh_svc_predict_device(tmh_svc* h, const double* dev_x, int64_t n, const double* dev_center,
+                           const double* dev_scale, int32_t* dev_labels, double* dev_dec,
+                           void* stream);
+int tmh_svc_predict(tmh_svc* h, const double* host_x, int64_t n, const double* host_center,
+                    const double* host_scale, int32_t* host_labels, double* host_dec);
+
 /* ---- device memory helpers for callers without another allocator -------- */
 int tmh_malloc_device(void** dev_ptr, size_t bytes);
 int tmh_free_device(void* dev_ptr);

@@ -8,14 +8,14 @@
 
 namespace tmh {
 
-static void check_table(const void* x, int64_t n, int d) {
+void check_table(const void* x, int64_t n, int d) {
   TMH_CHECK(x, TMH_EINVAL, "data pointer is NULL");
   TMH_CHECK(n >= 1 && n < ((int64_t)1 << 31), TMH_EINVAL, "n must be 1 .. 2^31 - 1 rows");
   TMH_CHECK(d >= 1 && d <= TMH_CLUSTER_MAX_D, TMH_EINVAL, "d is over the limit of 256 features");
   TMH_CHECK((reinterpret_cast<uintptr_t>(x) & 7) == 0, TMH_EINVAL, "data must be 8-byte aligned");
 }
 
-static void check_scaler(const double* center, const double* scale) {
+void check_scaler(const double* center, const double* scale) {
   TMH_CHECK((center == nullptr) == (scale == nullptr), TMH_EINVAL,
             "center and scale are given together or not at all");
 }
@@ -29,7 +29,7 @@ static void check_kmeans(const void* x, int64_t n, int d, int k, bool needs_k_ro
   TMH_CHECK(!needs_k_rows || k <= n, TMH_EINVAL, "more clusters than rows");
 }
 
-static bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
   const char* pa = static_cast<const char*>(a);
   const char* pb = static_cast<const char*>(b);
   return pa < pb + b_bytes && pb < pa + a_bytes;
@@ -47,8 +47,8 @@ static std::vector<unsigned long long> census_host(const double* dev_x, int64_t 
   return h;
 }
 
-static void require_finite(const double* dev_x, int64_t n, int d, DBuf<unsigned long long>& cnt,
-                           hipStream_t s) {
+void require_finite(const double* dev_x, int64_t n, int d, DBuf<unsigned long long>& cnt,
+                    hipStream_t s) {
   const std::vector<unsigned long long> h = census_host(dev_x, n, d, cnt, s);
   for (int f = 0; f < d; ++f)
     TMH_CHECK(h[(size_t)f] == (unsigned long long)n && h[(size_t)d + f] == 0, TMH_EINVAL,
@@ -312,21 +312,6 @@ static void seed_dev(const double* dev_x, int64_t n, int d, int k, const double*
                            s));
   TMH_HIP(hipStreamSynchronize(s));
 }
-
-// the host forms' staging: the table and the optional scaler on the device
-struct HostTable {
-  DBuf<double> x, center, scale;
-  void upload(const double* host_x, int64_t n, int d, const double* host_center,
-              const double* host_scale) {
-    check_table(host_x, n, d);
-    check_scaler(host_center, host_scale);
-    x.upload(host_x, (size_t)n * d);
-    if (host_center) {
-      center.upload(host_center, (size_t)d);
-      scale.upload(host_scale, (size_t)d);
-    }
-  }
-};
 
 }  // namespace tmh
 

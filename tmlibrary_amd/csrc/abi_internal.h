@@ -314,6 +314,29 @@ FixList corrector_fixlist(tmh_corrector* c, int64_t n_sites, hipStream_t s);  //
 void corrector_forms(tmh_corrector* c, hipStream_t s);
 void check_clip(int lo, int hi, int maxv);
 
+// feature tables of the clustering and classification tools (abi_cluster.hip)
+void check_table(const void* x, int64_t n, int d);
+void check_scaler(const double* center, const double* scale);
+bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes);
+// TMH_EINVAL when the table holds NaN or +-inf; cnt is the census' scratch (waits)
+void require_finite(const double* dev_x, int64_t n, int d, DBuf<unsigned long long>& cnt,
+                    hipStream_t s);
+
+// the host forms' staging: the table and the optional scaler on the device
+struct HostTable {
+  DBuf<double> x, center, scale;
+  void upload(const double* host_x, int64_t n, int d, const double* host_center,
+              const double* host_scale) {
+    check_table(host_x, n, d);
+    check_scaler(host_center, host_scale);
+    x.upload(host_x, (size_t)n * d);
+    if (host_center) {
+      center.upload(host_center, (size_t)d);
+      scale.upload(host_scale, (size_t)d);
+    }
+  }
+};
+
 }  // namespace tmh
 
 #pragma GCC visibility pop

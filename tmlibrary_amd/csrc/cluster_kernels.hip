@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "table_load.h"
 
 namespace tmh {
 
@@ -46,21 +47,6 @@ __device__ __forceinline__ unsigned long long f64_key(double v) {
 __device__ __forceinline__ double key_f64(unsigned long long k) {
   const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
   return __longlong_as_double((long long)u);
-}
-
-__device__ __forceinline__ double scaled(double v, const double* c, const double* s, int f) {
-  return c ? (v - c[f]) / s[f] : v;
-}
-
-// center / scale into LDS (sc[0..d) centres, sc[256..256+d) scales); the
-// caller synchronizes
-__device__ __forceinline__ void stage_scaler(const double* __restrict__ cen,
-                                             const double* __restrict__ scl, int d, double* sc) {
-  if (!cen) return;
-  for (int f = threadIdx.x; f < d; f += blockDim.x) {
-    sc[f] = cen[f];
-    sc[256 + f] = scl[f];
-  }
 }
 
 // rows [r0, r0 + rows) of X, scaled, into tile[rows][d]: 16-byte loads where

@@ -522,6 +522,26 @@ void cluster_seed_pick(const double* pots, int trials, const int64_t* cand, cons
                        const double* trial_closest, int64_t n, double* closest, hipStream_t s);
 void cluster_gather_rows(const double* X, int d, int k, const double* cen, const double* scl,
                          const int32_t* indices, double* centres, hipStream_t s);
+// the supervised classification tool (classify_kernels.hip, classify_core.h)
+struct ForestNode;
+constexpr int64_t kForestLdsBytes = 96 * 1024;  // packed nodes the LDS route stages
+// cnt[0] = finite values of X whose f32 cast is infinite
+void classify_count_f32_overflow(const double* X, int64_t n, int d, unsigned long long* cnt,
+                                 hipStream_t s);
+bool forest_fits_lds(int64_t nodes);
+int forest_tile_rows(int d, int n_classes, int n_trees);
+// proba (nullptr: labels only) [n][n_classes]
+void forest_predict(const double* X, int64_t n, int d, int n_classes, int n_trees, int nodes,
+                    bool lds_route, const ForestNode* dev_nodes, const int32_t* dev_roots,
+                    const double* dev_leaf_value, int32_t* labels, double* proba, hipStream_t s);
+// m rows of dev_sv: the support vectors (rbf; dev_coef [k - 1][m], dev_start
+// [k + 1]) or the pairs' weight vectors (linear; m = k (k - 1) / 2).  tile_cap
+// (0: none) caps the SVs per LDS tile; dec (nullptr: labels only) [n][k (k - 1) / 2]
+int svc_tile_svs(int d, int k, int kernel, int m, int cap);
+void svc_predict(const double* X, int64_t n, int d, int k, int kernel, double gamma, int m,
+                 int tile_cap, const double* cen, const double* scl, const double* dev_sv,
+                 const double* dev_coef, const int32_t* dev_start, const double* dev_rho,
+                 int32_t* labels, double* dec, hipStream_t s);
 // site-image input (inflate_kernels.hip)
 int64_t inflate_scratch_bytes(int64_t n_chunks, int64_t raw_max);
 void launch_inflate(const uint8_t* src, int64_t src_bytes, const tmh_zchunk* chunks,

@@ -30,6 +30,12 @@ TMH_OPT_HOST_STAGING = 5
 TMH_OPT_FUSED_CUS = 8
 TMH_OPT_FUSED_BANDS = 9
 TMH_FUSED_NO_HIST = 100
+TMH_OPT_FOREST_MEMORY_ROUTE = 20
+TMH_OPT_SVC_TILE = 21
+TMH_FOREST_ROUTE_LDS = 0
+TMH_FOREST_ROUTE_MEMORY = 1
+TMH_SVC_RBF = 0
+TMH_SVC_LINEAR = 1
 TMH_SYNTH_STANDARD = 0
 TMH_SYNTH_BRIGHT = 1
 TMH_SYNTH_UNIFORM = 2
@@ -155,6 +161,18 @@ SIGNATURES = {
                                    C.POINTER(_I), C.POINTER(_D), _P]),
     "tmh_kmeans_fit": (_I, [_P, _I64, _I, _I, _P, _P, _P, _I, _D, _P, _P, C.POINTER(_D),
                             C.POINTER(_I), C.POINTER(_D)]),
+    "tmh_forest_create": (_I, [_P, _P, _P, _P, _P, _I64, _P, _I, _P, _I64, _I, _I, C.POINTER(_P)]),
+    "tmh_forest_destroy": (None, [_P]),
+    "tmh_forest_set_option": (_I, [_P, _I, _I]),
+    "tmh_forest_route": (_I, [_P, C.POINTER(_I), C.POINTER(_I64)]),
+    "tmh_forest_predict_device": (_I, [_P, _P, _I64, _P, _P, _P]),
+    "tmh_forest_predict": (_I, [_P, _P, _I64, _P, _P]),
+    "tmh_svc_create": (_I, [_I, _D, _P, _I64, _I, _P, _I, _P, _P, C.POINTER(_P)]),
+    "tmh_svc_destroy": (None, [_P]),
+    "tmh_svc_set_option": (_I, [_P, _I, _I]),
+    "tmh_svc_tile": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "tmh_svc_predict_device": (_I, [_P, _P, _I64, _P, _P, _P, _P, _P]),
+    "tmh_svc_predict": (_I, [_P, _P, _I64, _P, _P, _P, _P]),
     "tmh_malloc_device": (_I, [C.POINTER(_P), C.c_size_t]),
     "tmh_free_device": (_I, [_P]),
     "tmh_memcpy": (_I, [_P, _P, C.c_size_t, _I, _P]),

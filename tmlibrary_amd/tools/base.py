@@ -10,8 +10,9 @@ a DataFrame works; pandas is imported only to hand back a Series when the
 input had an ``.index``.
 
 Differences by design: the database is an in-memory ``FeatureStore``;
-``KMeans`` runs ``n_init=1`` by default; the supervised tools (random forest,
-SVM with grid search) are not built.
+``KMeans`` runs ``n_init=1`` by default; the supervised models (random forest,
+SVM with grid search) live in ``tools/supervised.py`` and the ``Classification``
+tool overrides ``train_supervised``, which stays unbuilt on this base class.
 """
 from __future__ import annotations
 

@@ -28,6 +28,8 @@
 #   profh[:DIST]   prof with the HIP runtime trace (host waits) -> rocprof_h_DIST_TAG/
 #   pmc:DIST       FETCH_SIZE and WRITE_SIZE passes (each its own run) of a
 #                  short bench on DIST -> pmc_traffic_DIST_TAG.json
+#   pmcclassify[:D] SQ / GRBM counters of the forest and SVC predict kernels at
+#                  10^6 x D (default 20) -> pmc_sq_classification_TAG.json
 #   ab:R:LIB,LIB   same-box A/B of library builds (TMH_LIB), R rounds, the
 #                  order reversed every other round (ab_TAG.jsonl)
 #   ab432:R:LIB,.. the same over dist432 runs (ab432_TAG.jsonl)
@@ -214,6 +216,26 @@ for step in "$@"; do
       python3 tools/pmc_sq.py $O/pmcsq1_${D}_$TAG $O/pmcsq2_${D}_$TAG --pixels $((3456 * 2160 * 2560)) \
         -o $O/pmc_sq_${D}_$TAG.json > /dev/null || exit $?
       python3 -c "import json,sys; d=json.load(open(sys.argv[1])); [print(k[:60], v['derived']) for k, v in d['kernels'].items()]" $O/pmc_sq_${D}_$TAG.json
+      ;;
+    pmcclassify)
+      # SQ / GRBM counters of the classification kernels at
+      # 10^6 x D features, the device side of tools/bench_classification.py
+      # alone; the two passes of pmcsq, each its own run:
+      # pmcclassify[:D] -> pmc_sq_classification_TAG.json (kept as
+      # profiles/r18/pmc_sq_classification.json for D = 20)
+      D=${a1:-20}
+      PA="SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE"
+      PB="SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE"
+      n=0
+      for P in "$PA" "$PB"; do
+        n=$((n + 1))
+        timeout -s KILL 240 rocprofv3 --pmc $P --kernel-trace --output-format csv -d $O/pmc_classify${n}_$TAG -o run \
+          -- python3 tools/bench_classification.py --no-cpu --features $D --warmup 1 --reps 2 --out "" \
+          > $O/pmc_classify${n}_$TAG.log 2>&1 || exit $?
+      done
+      python3 tools/pmc_sq.py $O/pmc_classify1_$TAG $O/pmc_classify2_$TAG --pixels 1000000 \
+        --kernels k_forest_predict,k_svc_predict -o $O/pmc_sq_classification_$TAG.json > /dev/null || exit $?
+      python3 -c "import json,sys; d=json.load(open(sys.argv[1])); [print(k[:60], v['derived']) for k, v in d['kernels'].items()]" $O/pmc_sq_classification_$TAG.json
       ;;
     ab)
       IFS=, read -r -a LIBS <<< "$a2"
