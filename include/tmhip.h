@@ -93,17 +93,19 @@ int tmh_stats_reset(tmh_stats* h);
  * that way: ~0.5 s per 3,456 sites, against ~36 ms chosen right;
  * test_gpu_parity.py dark_prefix_wide_tail).  Force a configuration
  * (TMH_OPT_FUSED_CONFIG) for such jobs.
- *   TMH_OPT_FUSED_CONFIG   0..5: (sites per unit, threads, LDS bins) of the
- *                          fused correct+histogram pass = (2, 1024, 32768),
- *                          (4, 1024, 32768), (2, 512, 16384), (4, 512, 16384),
- *                          (1, 1024, 32768), (4, 1024, 65536 u16 counters
- *                          packed two sites to a word).  -1 (default): from
- *                          the probe -- 3; or 5 when >= 2% of the probed
- *                          groups hold a value >= 4,096; or, when >= 33% hold
- *                          a value >= 16,384 ("very wide" sites, e.g. uniform
- *                          16-bit data), the pass runs without its histogram
- *                          and a per-site u16-pair LDS histogram pass (one
- *                          more read) builds them; 100 forces that form.
+ *   TMH_OPT_FUSED_CONFIG   (sites per unit, threads, LDS bins) of the fused
+ *                          correct+histogram pass: 3 = (4, 512, 16384), 5 =
+ *                          (4, 1024, 65536 u16 counters packed two sites to a
+ *                          word).  -1 (default): from the probe -- 3; or 5
+ *                          when >= 2% of the probed groups hold a value >=
+ *                          4,096; or, when >= 33% hold a value >= 16,384
+ *                          ("very wide" sites, e.g. uniform 16-bit data), the
+ *                          pass runs without its histogram and a per-site
+ *                          u16-pair LDS histogram pass (one more read) builds
+ *                          them; 100 forces that form.  0, 1, 2 and 4 (one or
+ *                          two sites per unit, 32,768 u32 bins: 17.7 against
+ *                          16.0 ms on bright sites, common.h) were measured
+ *                          slower and removed: TMH_EINVAL.
  *   TMH_OPT_WELFORD_PARTS  0 (default): automatic -- with the log transform,
  *                          a launch of >= 96 sites whose job probe found >=
  *                          10% of the groups holding a value >= 4,096 (bright
@@ -112,19 +114,15 @@ int tmh_stats_reset(tmh_stats* h);
  *                          order), else one part; 1..4: that many parts where
  *                          the launch has >= 32 sites a part
  *   TMH_OPT_COPY_THREADS   1..64 (default 8): host threads of the pageable <->
- *                          pinned copies of the host-buffer entry points
- *   TMH_OPT_HOST_STAGING   host-buffer entry points: 0 = the caller's buffers
- *                          go straight to the copy engines; 1 = inputs AND
- *                          outputs through pinned slots; 2 (default) =
- *                          outputs only (the pageable H2D path is as fast as
- *                          a pinned bounce; a pinned D2H slot copied out by
- *                          several threads spreads a fresh output's faults) */
+ *                          pinned copies of the host-buffer entry points'
+ *                          outputs (inputs go straight from the caller's) */
 #define TMH_OPT_FUSED_CONFIG 1
 #define TMH_OPT_WELFORD_PARTS 2
 /* 3, 6 and 7 were TMH_OPT_TAIL_CHUNKS / TMH_OPT_PCT_TAIL / TMH_OPT_FUSED_EPOCHS
- * (percentile-tail variants measured slower than the default, removed) */
+ * (percentile-tail variants measured slower than the default, removed); 5 was
+ * TMH_OPT_HOST_STAGING (its other modes: a pinned input bounce slower than the
+ * runtime's pageable path, and an unpinned output; never selected, removed) */
 #define TMH_OPT_COPY_THREADS 4
-#define TMH_OPT_HOST_STAGING 5
 int tmh_stats_set_option(tmh_stats* h, int option, int value);
 
 /* update(image) for a run of sites.  zero_counts_out (host, n_sites, may be
@@ -215,7 +213,7 @@ int tmh_stats_wide_groups(tmh_stats* h, uint64_t* groups_out, int64_t* sites_out
  * options above): probe_counts[3] = groups sampled, groups with a value >=
  * 4,096, >= 16,384 (zeros before the probe ran); welford_bright = 1 / 0, -1
  * if the job has not been probed; fused_cfg = the configuration the fused
- * pass runs (0..5, or TMH_FUSED_NO_HIST).  Any output may be NULL. */
+ * pass runs (3, 5 or TMH_FUSED_NO_HIST).  Any output may be NULL. */
 #define TMH_FUSED_NO_HIST 100
 int tmh_stats_job_choice(tmh_stats* h, uint32_t* probe_counts, int* welford_bright,
                          int* fused_cfg);
@@ -310,8 +308,7 @@ void tmh_corrector_destroy(tmh_corrector* c);
  * no synchronisation): one corrector serves every job of the same shape. */
 int tmh_corrector_update_device(tmh_corrector* c, const double* dev_mean, const double* dev_std,
                                 void* stream);
-/* Options of a corrector: TMH_OPT_COPY_THREADS, TMH_OPT_HOST_STAGING (see
- * tmh_stats_set_option), and TMH_OPT_FUSED_CUS: the fused correct+histogram
+/* Options of a corrector: TMH_OPT_COPY_THREADS (see tmh_stats_set_option), and TMH_OPT_FUSED_CUS: the fused correct+histogram
  * pass's persistent grid spans this many CUs' worth of workgroups (0 or the
  * CU count, default: all) -- fewer leave room for other streams' kernels
  * (several channel jobs sharing a GPU).  Results never depend on them. */
@@ -349,7 +346,7 @@ int tmh_job_planes_multi_device(tmh_stats* const* hs, tmh_corrector* const* cs, 
                                 double* const* dev_smean, double* const* dev_sstd, double sigma,
                                 void* stream);
 /* Host buffers: chunks of <= 16 sites, H2D / kernel / D2H on three streams
- * with two device and two pinned output slots (TMH_OPT_HOST_STAGING).  Returns when host_out is
+ * with two device and two pinned output slots.  Returns when host_out is
  * complete; host_out must not overlap host_in. */
 int tmh_correct_u16(tmh_corrector* c, const uint16_t* host_in, uint16_t* host_out,
                     int64_t n_sites, int clip_lo, int clip_hi);

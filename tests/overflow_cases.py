@@ -206,7 +206,7 @@ def lds_set():
 
 
 FUSED_BANDS = (8, 16, 32, 64)  # tmhip.h TMH_OPT_FUSED_BANDS; fused_bands() doubles 8 / 16 up to 64
-FUSED_SPU = (2, 4)             # sites per unit of configurations 0..3 and 5 (fused_kernels.hip kFusedCfgs)
+FUSED_SPU = (4,)               # sites per unit of both configurations (fused_kernels.hip kNarrowCfg, kWideCfg)
 FIX_SH = 256                   # fused_kernels.hip kFixSh: a unit's LDS fixup set
 
 

@@ -92,8 +92,8 @@ def _job(L, torch, H, W, sites_np, shift, cfg=-1, order_seed=0):
 
 @pytest.mark.parametrize("kind,n,shift,cfg", [
     ("synthetic", 37, 2, -1),   # ragged last block (1 site), narrow configuration
-    ("bright", 100, 2, -1),     # probe -> 3 Welford parts, wide configuration (2 sites/unit)
-    ("synthetic", 100, 6, 1),   # 64-site blocks, a forced 4-site / 32,768-bin configuration
+    ("bright", 100, 2, -1),     # probe -> 3 Welford parts, wide configuration (4 sites/unit, packed)
+    ("synthetic", 100, 6, 5),   # 64-site blocks, the wide configuration forced on dark sites
     ("uniform", 13, 3, -1),     # very wide: no-histogram fused pass + u16 LDS histograms
 ])
 def test_blocked_equals_contiguous(kind, n, shift, cfg):

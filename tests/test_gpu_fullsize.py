@@ -266,7 +266,7 @@ def _wide_groups(sites):
     return int(np.count_nonzero((g >= 4096).any(axis=2)))
 
 
-@pytest.mark.parametrize("cfg", [-1, 0, 1, 2, 3, 4, 5])
+@pytest.mark.parametrize("cfg", [-1, 3, 5])
 def test_fused_multi_job_configs(L, cfg):
     """cfg -1 is the automatic choice: job 1 is bright (lognormal(8.5, 0.6)),
     so the Welford count must select the wide configuration for it, and the

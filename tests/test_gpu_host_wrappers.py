@@ -100,3 +100,42 @@ def test_shrink_returns_an_odd_mosaics_tile_as_passed_in(L):
                                     C.byref(ow)))
     assert (oh.value, ow.value) == (127, 128)
     assert np.array_equal(dst, keep)
+
+
+def test_retired_option_values_are_refused(L):
+    """Option values whose code paths were removed (fused configurations 0, 1,
+    2 and 4; option 5, the host staging mode) are TMH_EINVAL, the remaining
+    ones are accepted and reported back; the option calls launch no kernel."""
+    from tmlibrary_amd import hip
+    from tmlibrary_amd.workflow.corilla.quantiles import quantile_table, stats_log10_lut
+    H = W = 32
+    lo, hi, gamma = quantile_table(H * W, np.linspace(0, 100, 1000))
+    lut = stats_log10_lut()
+    h = C.c_void_p()
+    hip.check(L.tmh_stats_create(H, W, 1000, hip.ptr(lo), hip.ptr(hi), hip.ptr(gamma),
+                                 hip.ptr(lut), 1, 0, C.byref(h)))
+    c = C.c_void_p()
+    mean, std = np.full((H, W), 2.5), np.full((H, W), 0.15)
+    hip.check(L.tmh_corrector_create(hip.ptr(mean), hip.ptr(std), H, W, 1, -10.0, C.byref(c)))
+    try:
+        for v in (0, 1, 2, 4, 6, -2):
+            rc, msg = _fails(L, L.tmh_stats_set_option(h, hip.TMH_OPT_FUSED_CONFIG, v))
+            assert rc == hip.TMH_EINVAL, v
+            assert ("retired" in msg) == (v in (0, 1, 2, 4)), (v, msg)
+        fc = C.c_int(-7)
+        for v in (-1, 3, 5, 100):
+            assert L.tmh_stats_set_option(h, hip.TMH_OPT_FUSED_CONFIG, v) == hip.TMH_OK, v
+            hip.check(L.tmh_stats_job_choice(h, None, None, C.byref(fc)))
+            assert fc.value == (3 if v == -1 else v), (v, fc.value)  # unprobed: narrow
+        assert hip.TMH_FUSED_NO_HIST == 100
+        for set_option, handle in ((L.tmh_stats_set_option, h), (L.tmh_corrector_set_option, c)):
+            rc, msg = _fails(L, set_option(handle, 5, 2))
+            assert rc == hip.TMH_EINVAL and "unknown" in msg, msg
+            for v in (1, 64):
+                assert set_option(handle, hip.TMH_OPT_COPY_THREADS, v) == hip.TMH_OK, v
+            for v in (0, 65):
+                rc, msg = _fails(L, set_option(handle, hip.TMH_OPT_COPY_THREADS, v))
+                assert rc == hip.TMH_EINVAL and msg == "copy threads must be 1..64", (v, msg)
+    finally:
+        L.tmh_corrector_destroy(c)
+        L.tmh_stats_destroy(h)

@@ -105,17 +105,6 @@ def test_tiles_base_host_form_any_table_order(L, cases):
     assert np.array_equal(out, want)
 
 
-def test_tiles_base_aligned_pair_loads(L, cases, monkeypatch):
-    """The alternative source-load form (TMH_TILES_LOADS=pair, kept for
-    measurement) gives the same bytes."""
-    from tmlibrary_amd.workflow.pyramid import build_pyramid
-    monkeypatch.setenv("TMH_TILES_LOADS", "pair")
-    for name in ("two_wells", "displaced"):
-        g, sites, want, _ = cases(name)
-        with build_pyramid(g, sites) as pyr:
-            assert np.array_equal(pyr.level(pyr.depth - 1), _stitch(want))
-
-
 # ---- shrink -------------------------------------------------------------------------
 
 def _shrink_host_form(L, level, last_h, last_w, fill=0xAA):

@@ -411,14 +411,11 @@ int tmh_correct_u16(tmh_corrector* c, const uint16_t* host_in, uint16_t* host_ou
     }
     HostPipe& p = c->pipe;
     p.init();
-    const bool pinned_in = c->host.staging == kStagingPinnedIn,
-               pinned_out = c->host.staging != kStagingDirect;
     auto retire = [&](int slot) {
       if (!p.busy[slot]) return;
       TMH_HIP(hipEventSynchronize(p.ev_done[slot]));
-      if (pinned_out)
-        par_copy(host_out + p.s0[slot] * c->npx, p.out[slot].p, (size_t)p.ns[slot] * c->npx * 2,
-                 c->host.copy_threads);
+      par_copy(host_out + p.s0[slot] * c->npx, p.out[slot].p, (size_t)p.ns[slot] * c->npx * 2,
+               c->host.copy_threads);
       p.busy[slot] = false;
     };
     int64_t k = 0;
@@ -428,20 +425,10 @@ int tmh_correct_u16(tmh_corrector* c, const uint16_t* host_in, uint16_t* host_ou
         const int64_t ns = std::min(step, n_sites - s0);
         const size_t bytes = (size_t)ns * c->npx * 2;
         retire(slot);  // chunk k-2: output copied out, both slot buffers free
-        const void* src = host_in + s0 * c->npx;
-        void* dst = host_out + s0 * c->npx;
-        if (pinned_in) {
-          p.in[slot].ensure(slot_px * 2);
-          par_copy(p.in[slot].p, src, bytes, c->host.copy_threads);
-          src = p.in[slot].p;
-        }
-        if (pinned_out) {
-          p.out[slot].ensure(slot_px * 2);
-          dst = p.out[slot].p;
-        }
+        p.out[slot].ensure(slot_px * 2);
         uint16_t* din = c->stage_in.p + (size_t)slot * slot_px;
         uint16_t* dout = c->stage_out.p + (size_t)slot * slot_px;
-        TMH_HIP(hipMemcpyAsync(din, src, bytes, hipMemcpyHostToDevice, p.h2d));
+        TMH_HIP(hipMemcpyAsync(din, host_in + s0 * c->npx, bytes, hipMemcpyHostToDevice, p.h2d));
         TMH_HIP(hipEventRecord(p.ev_in[slot], p.h2d));
         TMH_HIP(hipStreamWaitEvent(c->stream, p.ev_in[slot], 0));
         const FixList fl = corrector_fixlist(c, ns, c->stream);
@@ -452,7 +439,7 @@ int tmh_correct_u16(tmh_corrector* c, const uint16_t* host_in, uint16_t* host_ou
                            clip_lo, clip_hi, c->stream);
         TMH_HIP(hipEventRecord(p.ev_kern[slot], c->stream));
         TMH_HIP(hipStreamWaitEvent(p.d2h, p.ev_kern[slot], 0));
-        TMH_HIP(hipMemcpyAsync(dst, dout, bytes, hipMemcpyDeviceToHost, p.d2h));
+        TMH_HIP(hipMemcpyAsync(p.out[slot].p, dout, bytes, hipMemcpyDeviceToHost, p.d2h));
         TMH_HIP(hipEventRecord(p.ev_done[slot], p.d2h));
         p.busy[slot] = true;
         p.s0[slot] = s0;

@@ -96,35 +96,24 @@ struct PinBuf {
 // memcpy between pageable and pinned host memory on up to max_t threads (abi_core.hip)
 void par_copy(void* dst, const void* src, size_t bytes, int max_t);
 
-// Staging of the host-buffer entry points (TMH_OPT_HOST_STAGING).  Measured
-// on MI355X boxes (tools/diag_host.py, bench extras.host_path): the runtime's
-// own pageable H2D path already reaches ~56 GB/s, above a pinned bounce fed by
-// 8 host threads, so by default inputs go straight from the caller's buffer;
-// outputs land in pinned slots and are copied out by several threads, which
-// also spreads the first-touch page faults of a fresh numpy output.
-// 0: everything direct; 1: inputs through pinned slots too; 2 (default).
-constexpr int kStagingDirect = 0, kStagingPinnedIn = 1, kStagingPinnedOut = 2;
-
+// Staging of the host-buffer entry points.  Measured on MI355X boxes
+// (tools/diag_host.py, bench extras.host_path): the runtime's own pageable H2D
+// path already reaches ~56 GB/s, above a pinned bounce fed by 8 host threads,
+// so inputs go straight from the caller's buffer; outputs land in pinned slots
+// and are copied out by copy_threads threads, which also spreads the
+// first-touch page faults of a fresh numpy output.
 struct HostOpts {
   int copy_threads = 8;
-  int staging = kStagingPinnedOut;
   bool set(int option, int value) {
-    if (option == TMH_OPT_COPY_THREADS) {
-      TMH_CHECK(value >= 1 && value <= 64, TMH_EINVAL, "copy threads must be 1..64");
-      copy_threads = value;
-      return true;
-    }
-    if (option == TMH_OPT_HOST_STAGING) {
-      TMH_CHECK(value >= 0 && value <= 2, TMH_EINVAL, "host staging must be 0, 1 or 2");
-      staging = value;
-      return true;
-    }
-    return false;
+    if (option != TMH_OPT_COPY_THREADS) return false;
+    TMH_CHECK(value >= 1 && value <= 64, TMH_EINVAL, "copy threads must be 1..64");
+    copy_threads = value;
+    return true;
   }
 };
 
 struct HostPipe {
-  PinBuf in[2], out[2];
+  PinBuf out[2];
   hipStream_t h2d = nullptr, d2h = nullptr;
   hipEvent_t ev_in[2]{}, ev_kern[2]{}, ev_done[2]{};
   bool busy[2] = {false, false};
@@ -193,7 +182,7 @@ struct tmh_stats {
   int join_n = 0;
   int fused_cfg = kFusedAuto;     // TMH_OPT_FUSED_CONFIG (-1: per launch, on the device)
   int wf_parts = 0;               // TMH_OPT_WELFORD_PARTS (0: automatic)
-  HostOpts host;                  // TMH_OPT_COPY_THREADS / TMH_OPT_HOST_STAGING
+  HostOpts host;                  // TMH_OPT_COPY_THREADS
   bool hist_dirty = false;        // a fused launch may have left counts / round masks behind
   int64_t n = 0;              // sites accumulated (Welford count)
   int64_t n_deferred = 0;     // sites whose order statistics are stored
@@ -252,7 +241,7 @@ struct tmh_corrector {
   DBuf<uint16_t> stage_in, stage_out;
   DBuf<uint8_t> stage8_in, stage8_out;
   HostPipe pipe;
-  HostOpts host;  // TMH_OPT_COPY_THREADS / TMH_OPT_HOST_STAGING
+  HostOpts host;  // TMH_OPT_COPY_THREADS
   // a histogram tail still reading queues (round masks) on a statistics
   // handle's stream (correct_hist_dev, cross-stream calls)
   hipEvent_t ev_tail = nullptr;

@@ -314,7 +314,10 @@ int tmh_stats_set_option(tmh_stats* h, int option, int value) {
     TMH_CHECK(h, TMH_EINVAL, "handle is NULL");
     switch (option) {
       case TMH_OPT_FUSED_CONFIG:
-        TMH_CHECK((value >= kFusedAuto && value < kFusedConfigs) || value == kFusedNoHist,
+        TMH_CHECK(value < 0 || value > 4 || value == kFusedNarrow, TMH_EINVAL,
+                  "fused configuration retired (measured slower): 3, 5 and 100 remain");
+        TMH_CHECK(value == kFusedAuto || value == kFusedNarrow || value == kFusedWide ||
+                      value == kFusedNoHist,
                   TMH_EINVAL, "fused configuration out of range");
         h->fused_cfg = value;
         break;
@@ -434,7 +437,6 @@ int tmh_stats_update(tmh_stats* h, const uint16_t* host_sites, int64_t n_sites, 
       h->stage.ensure(2 * slot_px);
     }
     p.init();
-    const bool pinned = h->host.staging == kStagingPinnedIn;
     // retire chunk k-2 of this slot: its H2D, kernels and zero-count copy
     auto retire = [&](int slot) {
       if (!p.busy[slot]) return;
@@ -451,14 +453,8 @@ int tmh_stats_update(tmh_stats* h, const uint16_t* host_sites, int64_t n_sites, 
         const size_t bytes = (size_t)ns * h->npx * 2;
         retire(slot);
         p.out[slot].ensure((size_t)per * 8);
-        const void* src = host_sites + s0 * h->npx;
-        if (pinned) {
-          p.in[slot].ensure(slot_px * 2);
-          par_copy(p.in[slot].p, src, bytes, h->host.copy_threads);
-          src = p.in[slot].p;
-        }
         uint16_t* dev = h->stage.p + (size_t)slot * slot_px;
-        TMH_HIP(hipMemcpyAsync(dev, src, bytes, hipMemcpyHostToDevice, p.h2d));
+        TMH_HIP(hipMemcpyAsync(dev, host_sites + s0 * h->npx, bytes, hipMemcpyHostToDevice, p.h2d));
         TMH_HIP(hipEventRecord(p.ev_in[slot], p.h2d));
         TMH_HIP(hipStreamWaitEvent(hstream(h), p.ev_in[slot], 0));
         stats_update_dev(h, dev, ns, log_transform, hstream(h));

@@ -427,14 +427,9 @@ void launch_smooth_planes(const double* const* in, double* const* out, double* c
       a.psum[k] = psum[k];
       a.pmin[k] = pmin ? pmin[k] : nullptr;
     }
-    // k_smooth_2d_blk needs H, W > R (one reflection); TMH_SMOOTH_FORM=0 picks
-    // the round-5 form (A/B)
-    static const bool blk = [] {
-      const char* e = getenv("TMH_SMOOTH_FORM");
-      return !(e && atoi(e) == 0);
-    }();
+    // k_smooth_2d_blk needs H, W > R (one reflection)
     const dim3 g((unsigned)cdiv(W, kSumTW), (unsigned)cdiv(H, kSumTH), (unsigned)np);
-    if (blk && H > 20)
+    if (H > 20)
       hipLaunchKernelGGL(k_smooth_2d_blk, g, dim3(256), 0, s, a, H, W, d_w);
     else
       hipLaunchKernelGGL((k_smooth_2d<kSumTH, 20>), g, dim3(256), 0, s, a, H, W, d_w);

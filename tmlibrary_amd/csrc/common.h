@@ -377,16 +377,15 @@ void launch_correct_u8(const uint8_t* in, uint8_t* out, int64_t npx, int64_t n_s
                        const float4* coef, const float2* lut, const float4* mconst,
                        const FixList& fl, int log_transform, int clip_lo, int clip_hi,
                        hipStream_t s);
-// fused pass configurations (fused_kernels.hip kFusedCfgs).  kFusedAuto picks
+// fused pass configurations (fused_kernels.hip kNarrowCfg, kWideCfg; the
+// numbers are the public ones of TMH_OPT_FUSED_CONFIG).  kFusedAuto picks
 // per job on the host from the site probe: kFusedNarrow (four sites per unit,
 // 4,096-bin slices) unless at least kWideFrac of the probed pixel groups hold
-// a value >= 4,096, then kFusedWide: four sites, 16,384 bins
-// each as u16 counters packed two sites to a word (round 3: 15.95-16.11 ms
-// on 3,456 bright sites against 17.67-17.75 for configuration 0's two sites
-// x 16,384 u32 bins, profiles/r3/ab_fused_packed_bright_r3z20.jsonl; round 2:
-// configuration 0 18.6 ms against 22.4 for one site x 32,768 bins and 231 ms
-// narrow, profiles/r2/mb_fused_bright_r2f.txt).
-constexpr int kFusedConfigs = 6;
+// a value >= 4,096, then kFusedWide: four sites, 16,384 bins each as u16
+// counters packed two sites to a word.  The retired shapes 0, 1, 2 and 4 (one
+// or two sites per unit, 32,768 u32 bins) lost to these: 17.67-17.75 ms against
+// 15.95-16.11 on bright sites (profiles/r3/ab_fused_packed_bright_r3z20.jsonl),
+// 22.4 against 18.6 (profiles/r2/mb_fused_bright_r2f.txt).
 constexpr int kFusedQueueInts = 16;  // fused pass scratch: 8 unit counters + 64-bit round union
 constexpr int kFusedAuto = -1;
 constexpr int kFusedNarrow = 3;
@@ -426,7 +425,7 @@ struct FusedJobs {
   FusedJob j[kMaxJobs];
   int n;
 };
-// cfg: 0 .. kFusedConfigs - 1 or kFusedNoHist -- exactly one launch; bands:
+// cfg: kFusedNarrow, kFusedWide or kFusedNoHist -- exactly one launch; bands:
 // pixel bands of the unit sweep (0: the configuration's, more for a short
 // launch -- fused_kernels.hip fused_bands)
 void launch_correct_hist(const FusedJobs& J, int64_t npx, int log_transform, int clip_lo,

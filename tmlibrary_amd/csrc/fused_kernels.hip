@@ -615,20 +615,11 @@ struct FusedCfg {
   int spu, threads, lds_bins, bands;
   bool packed;  // u16 counters, two sites per word (k_correct_hist PK)
 };
-constexpr FusedCfg kFusedCfgs[kFusedConfigs] = {{2, 1024, 32768, 8, false},
-                                                {4, 1024, 32768, kFusedBands, false},
-                                                {2, 512, 16384, kFusedBands, false},
-                                                {4, 512, 16384, kFusedBands, false},
-                                                {1, 1024, 32768, kFusedBands, false},
-                                                {4, 1024, 65536, 8, true}};
-template <int K>
-struct FusedCfgCheck {
-  static_assert((kFusedCfgs[K].lds_bins / kFusedCfgs[K].spu) % 1024 == 0,
-                "LDS slices must cover whole 1,024-bin rounds");
-  static constexpr bool ok = true;
-};
-static_assert(FusedCfgCheck<0>::ok && FusedCfgCheck<1>::ok && FusedCfgCheck<2>::ok &&
-              FusedCfgCheck<3>::ok && FusedCfgCheck<4>::ok && FusedCfgCheck<5>::ok, "");
+constexpr FusedCfg kNarrowCfg = {4, 512, 16384, kFusedBands, false};
+constexpr FusedCfg kWideCfg = {4, 1024, 65536, 8, true};
+static_assert((kNarrowCfg.lds_bins / kNarrowCfg.spu) % 1024 == 0 &&
+                  (kWideCfg.lds_bins / kWideCfg.spu) % 1024 == 0,
+              "LDS slices must cover whole 1,024-bin rounds");
 
 // Pixel bands of a launch: the configuration's, doubled (up to 64) while the
 // launch has fewer than 8 units per workgroup -- a short launch (a rank's
@@ -643,6 +634,26 @@ static int fused_bands(int cfg_bands, int64_t n_sites, int spu, int64_t n_wgs, i
   return b;
 }
 
+// One shape of the fused pass (ABL 1: without its histogram) over the jobs of J.
+template <bool LOG, bool WIDE, int ABL>
+static void launch_shape(const FusedJobs& J, int64_t npx, int clip_lo, int clip_hi, int* queues,
+                         int n_wg, int bands_opt, hipStream_t s) {
+  constexpr FusedCfg c = WIDE ? kWideCfg : kNarrowCfg;
+  const dim3 grid(n_wg * (1024 / c.threads));
+  int64_t n_sites = 0;  // the bands see the launch's site groups, every job's
+  for (int j = 0; j < J.n; ++j) n_sites += (J.j[j].n_sites + c.spu - 1) / c.spu * c.spu;
+  const int nbands = fused_bands(c.bands, n_sites, c.spu, grid.x, bands_opt);
+  FusedJobs Jc = J;
+  if (!c.packed)
+    for (int j = 0; j < J.n; ++j) Jc.j[j].rl = RareList{};
+  if (clip_lo >= 0)
+    hipLaunchKernelGGL((k_correct_hist<LOG, true, c.spu, ABL, c.threads, c.lds_bins, c.packed>),
+                       grid, dim3(c.threads), 0, s, Jc, npx, clip_lo, clip_hi, nbands, queues);
+  else
+    hipLaunchKernelGGL((k_correct_hist<LOG, false, c.spu, ABL, c.threads, c.lds_bins, c.packed>),
+                       grid, dim3(c.threads), 0, s, Jc, npx, clip_lo, clip_hi, nbands, queues);
+}
+
 // One launch of configuration cfg over the jobs of J (chosen by the caller:
 // abi_fused.hip picks it per job from the host-read site probe, so no losing
 // configuration is queued).  The caller zeroed queues and every job's uni.
@@ -655,40 +666,14 @@ void launch_correct_hist(const FusedJobs& J, int64_t npx, int log_transform, int
                          hipStream_t s) {
   if (J.n <= 0) return;
   ProfScope prof("correct_hist", s);
-  int64_t n_sites = 0;  // the bands see the launch's site groups, every job's
-#define TMH_LAUNCH_CH(L_, K_, A_)                                                                \
-  {                                                                                              \
-    constexpr FusedCfg c = kFusedCfgs[K_];                                                       \
-    const dim3 grid(n_wg * (1024 / c.threads));                                                  \
-    for (int j = 0; j < J.n; ++j) n_sites += (J.j[j].n_sites + c.spu - 1) / c.spu * c.spu;      \
-    const int nbands = fused_bands(c.bands, n_sites, c.spu, grid.x, bands_opt);                  \
-    FusedJobs Jc = J;                                                                            \
-    if (!c.packed)                                                                               \
-      for (int j = 0; j < J.n; ++j) Jc.j[j].rl = RareList{};                                     \
-    if (clip_lo >= 0)                                                                            \
-      hipLaunchKernelGGL((k_correct_hist<L_, true, c.spu, A_, c.threads, c.lds_bins, c.packed>), \
-                         grid, dim3(c.threads), 0, s, Jc, npx, clip_lo, clip_hi, nbands, queues); \
-    else                                                                                         \
-      hipLaunchKernelGGL((k_correct_hist<L_, false, c.spu, A_, c.threads, c.lds_bins, c.packed>), \
-                         grid, dim3(c.threads), 0, s, Jc, npx, clip_lo, clip_hi, nbands, queues); \
+  const bool lg = log_transform != 0;
+  const auto run = [&](auto* shape) { shape(J, npx, clip_lo, clip_hi, queues, n_wg, bands_opt, s); };
+  switch (cfg) {
+    case kFusedNarrow: run(lg ? launch_shape<true, false, 0> : launch_shape<false, false, 0>); break;
+    case kFusedWide: run(lg ? launch_shape<true, true, 0> : launch_shape<false, true, 0>); break;
+    case kFusedNoHist: run(lg ? launch_shape<true, false, 1> : launch_shape<false, false, 1>); break;
+    default: throw Error{TMH_EINVAL, "launch_correct_hist: no such fused configuration"};
   }
-#define TMH_LAUNCH_CFG(L_)                                     \
-  switch (cfg) {                                               \
-    case 0: TMH_LAUNCH_CH(L_, 0, 0) break;                     \
-    case 1: TMH_LAUNCH_CH(L_, 1, 0) break;                     \
-    case 2: TMH_LAUNCH_CH(L_, 2, 0) break;                     \
-    case 3: TMH_LAUNCH_CH(L_, 3, 0) break;                     \
-    case 5: TMH_LAUNCH_CH(L_, 5, 0) break;                     \
-    case kFusedNoHist: TMH_LAUNCH_CH(L_, kFusedNarrow, 1) break; \
-    default: TMH_LAUNCH_CH(L_, 4, 0) break;                    \
-  }
-  if (log_transform) {
-    TMH_LAUNCH_CFG(true);
-  } else {
-    TMH_LAUNCH_CFG(false);
-  }
-#undef TMH_LAUNCH_CFG
-#undef TMH_LAUNCH_CH
   TMH_HIP(hipGetLastError());
 }
 

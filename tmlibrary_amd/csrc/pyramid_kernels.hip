@@ -4,8 +4,6 @@
 // [tile_rows][tile_cols][256][256] uint8, every tile 64 KB contiguous; a
 // ragged tile (last row / column of a level) sits in its tile's top left
 // corner at the same 256-byte row pitch, zeros around it.
-#include <cstdlib>
-
 #include "common.h"
 
 namespace tmh {
@@ -24,30 +22,6 @@ __device__ __forceinline__ pyr_u32x4 load16_any(const uint8_t* p) {
   return v;
 }
 
-// The same bytes from the two aligned 16-byte blocks that hold them, shifted
-// into place; blocks that would leave [base, end) take the unaligned load.
-__device__ __forceinline__ pyr_u32x4 load16_pair(const uint8_t* p, const uint8_t* base,
-                                                 const uint8_t* end) {
-  const unsigned sh = (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u);
-  const uint8_t* a = p - sh;
-  if (a < base || a + (sh ? 32 : 16) > end) return load16_any(p);
-  const pyr_u32x4 lo = *reinterpret_cast<const pyr_u32x4*>(a);
-  if (sh == 0) return lo;
-  const pyr_u32x4 hi = *reinterpret_cast<const pyr_u32x4*>(a + 16);
-  const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  const unsigned ws = sh >> 2, bs = (sh & 3u) * 8u;
-  uint32_t t[5];
-#pragma unroll
-  for (int i = 0; i < 5; ++i)
-    t[i] = ws == 0 ? w[i] : ws == 1 ? w[i + 1] : ws == 2 ? w[i + 2] : w[i + 3];
-  pyr_u32x4 v;
-  v.x = __builtin_amdgcn_alignbit(t[1], t[0], bs);
-  v.y = __builtin_amdgcn_alignbit(t[2], t[1], bs);
-  v.z = __builtin_amdgcn_alignbit(t[3], t[2], bs);
-  v.w = __builtin_amdgcn_alignbit(t[4], t[3], bs);
-  return v;
-}
-
 // One workgroup per tile; a thread owns the 16-byte column group (tid & 15)
 // of the 16 rows (tid >> 4) + 16 j and writes each of them once: the bytes of
 // the tile's rectangle that covers them, else 0.
@@ -59,11 +33,11 @@ __device__ __forceinline__ pyr_u32x4 load16_pair(const uint8_t* p, const uint8_t
 // borders, background, spacer tiles -- take the general path: every rectangle
 // against the row, byte loads where one covers part of the group.  The
 // rectangles of a tile are disjoint, so the order does not matter.
-// PAIR: source groups as two aligned loads + shift instead of one unaligned.
+// (site_bytes_total, the sites' extent, is not read: the unaligned loads stay
+// inside their rectangle.)
 constexpr int kBatch = 8;
 constexpr int kXcds = 8;
 
-template <bool PAIR>
 __global__ __launch_bounds__(256) void k_tiles_base(const uint8_t* __restrict__ sites,
                                                     int64_t site_bytes_total, int H, int W,
                                                     const tmh_tile_rect* __restrict__ rects,
@@ -80,7 +54,6 @@ __global__ __launch_bounds__(256) void k_tiles_base(const uint8_t* __restrict__ 
   const int cx = (threadIdx.x & 15) * 16;
   const int r0 = threadIdx.x >> 4;
   uint8_t* dst = tiles + t * kTileBytes + cx;
-  const uint8_t* end = sites + site_bytes_total;
   unsigned done = 0;  // bit j: row r0 + 16 j is written
   for (int k = b; k < e; ++k) {
     const tmh_tile_rect q = rects[k];
@@ -94,8 +67,7 @@ __global__ __launch_bounds__(256) void k_tiles_base(const uint8_t* __restrict__ 
 #pragma unroll
       for (int i = 0; i < kBatch; ++i) {
         const int dy = min(max(first + 16 * i, 0), q.height - 1);
-        const uint8_t* p = src + (int64_t)dy * W;
-        v[i] = PAIR ? load16_pair(p, sites, end) : load16_any(p);
+        v[i] = load16_any(src + (int64_t)dy * W);
       }
 #pragma unroll
       for (int i = 0; i < kBatch; ++i) {
@@ -186,23 +158,15 @@ __global__ __launch_bounds__(256) void k_pyramid_shrink2(const uint8_t* __restri
 
 }  // namespace
 
-// TMH_TILES_LOADS=pair (env, read at each launch) selects the aligned-pair
-// source loads, measured against the default's unaligned ones
 void launch_tiles_base(const uint8_t* sites, int64_t n_sites, int H, int W,
                        const tmh_tile_rect* d_rects, const int* d_tbeg, uint8_t* tiles,
                        int64_t n_tiles, hipStream_t s) {
   ProfScope prof("tiles_base", s);
-  const char* e = getenv("TMH_TILES_LOADS");
-  const bool pair = e && e[0] == 'p';
   const int64_t total = n_sites * H * W;
   const int64_t per_xcd = cdiv(n_tiles, kXcds);
   const dim3 grid((unsigned)(per_xcd * kXcds));
-  if (pair)
-    hipLaunchKernelGGL(k_tiles_base<true>, grid, dim3(256), 0, s, sites, total, H, W, d_rects,
-                       d_tbeg, tiles, n_tiles, per_xcd);
-  else
-    hipLaunchKernelGGL(k_tiles_base<false>, grid, dim3(256), 0, s, sites, total, H, W, d_rects,
-                       d_tbeg, tiles, n_tiles, per_xcd);
+  hipLaunchKernelGGL(k_tiles_base, grid, dim3(256), 0, s, sites, total, H, W, d_rects, d_tbeg,
+                     tiles, n_tiles, per_xcd);
   TMH_HIP(hipGetLastError());
 }
 

@@ -26,7 +26,6 @@ TMH_STATS_SERIAL = 4
 TMH_OPT_FUSED_CONFIG = 1
 TMH_OPT_WELFORD_PARTS = 2
 TMH_OPT_COPY_THREADS = 4
-TMH_OPT_HOST_STAGING = 5
 TMH_OPT_FUSED_CUS = 8
 TMH_OPT_FUSED_BANDS = 9
 TMH_FUSED_NO_HIST = 100
