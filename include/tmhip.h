@@ -886,6 +886,42 @@ int tmh_object_contours(const int32_t* host_planes, int64_t n_planes, int height
                         int32_t* host_points, int64_t point_capacity, int64_t* n_contours,
                         int64_t* n_points);
 
+/* Input, SegmentationImage.create_from_polygons (tmlib/image.py:740-776) for
+ * every plane of a site in one call: the label planes of stored outlines.
+ * points is int32 [n_points][2], the rings' vertices one after the other as
+ * global map (x, y) pairs (exteriors only: the reference ignores holes, so
+ * they are filled); ring p is points first[p] .. first[p + 1] (int64
+ * [n_polygons + 1]) and is drawn with label[p] into plane plane[p] (int32
+ * [n_polygons] each).  The rings of one plane follow each other in the order
+ * of the reference's list: where two overlap, the one later in the arrays
+ * wins.  On load xs = x - x_offset and ys = -y - y_offset; the pixels of a
+ * ring are those skimage.draw.polygon of scikit-image 0.13.0 gives for (ys,
+ * xs) on a height x width plane (an even-odd test against every edge, exact
+ * for integer vertices; a repeated closing vertex changes nothing, a ring of
+ * one or two vertices fills nothing).  planes_out is int32
+ * [n_planes][height][width], zeroed by the call; any int32 label is written
+ * as given.  The bit rows of a ring's clipped bounding box (height of the box
+ * x ceil(width of the box / 64) words) sit in LDS up to TMH_POLYGON_LDS_WORDS
+ * words; a larger box is drawn through a workspace in memory: the same
+ * result.  The same input gives the same bytes on every run.
+ * TMH_EINVAL with nothing written: an empty ring, first not monotone (or
+ * first[0] < 0), a plane index outside 0 .. n_planes - 1, a transformed
+ * coordinate of magnitude 2^24 or more, planes_out overlapping an input, more
+ * than 65,535 planes, 2^31 - 1 rings or more.  n_polygons = 0 gives zero
+ * planes.  The device form reads the lists on `stream` (NULL: the default
+ * stream) to check them, waits, then queues the work there and returns when
+ * the planes are complete. */
+#define TMH_POLYGON_LDS_WORDS 512
+int tmh_polygon_fill_device(const int32_t* dev_points, const int64_t* dev_first,
+                            const int32_t* dev_plane, const int32_t* dev_label,
+                            int64_t n_polygons, int64_t n_planes, int height, int width,
+                            int64_t y_offset, int64_t x_offset, int32_t* dev_planes_out,
+                            void* stream);
+int tmh_polygon_fill(const int32_t* host_points, const int64_t* host_first,
+                     const int32_t* host_plane, const int32_t* host_label, int64_t n_polygons,
+                     int64_t n_planes, int height, int width, int64_t y_offset, int64_t x_offset,
+                     int32_t* host_planes_out);
+
 /* ---- the clustering tool -------------------------------------------------
  * tmlib/tools/clustering.py:40-99 through Classifier.train_unsupervised /
  * predict (tmlib/tools/base.py:586-645): RobustScaler(quantile_range=(1, 99))

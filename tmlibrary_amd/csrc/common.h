@@ -480,6 +480,16 @@ void contours_write(const int32_t* planes, int H, int W, int32_t max_label,
                     const tmh_object_row* rows, tmh_contour_object* objects,
                     const ContourScratch& scratch, tmh_contour* contours, int32_t* points,
                     hipStream_t s);
+// jterator object input (polygon_kernels.hip): the checks that read the lists
+// (TMH_EINVAL by name, nothing written), then the planes zeroed and drawn.
+// check: polygons_check_bytes() of device scratch shared by both.
+int64_t polygons_check_bytes();
+void polygons_check(const int32_t* points, const int64_t* first, const int32_t* plane,
+                    int64_t n_polygons, int64_t n_planes, int64_t y_offset, int64_t x_offset,
+                    void* check, int64_t* n_points, hipStream_t s);
+void polygons_fill(const int32_t* points, const int64_t* first, const int32_t* plane,
+                   const int32_t* label, int64_t n_polygons, int64_t n_planes, int H, int W,
+                   int64_t y_offset, int64_t x_offset, int32_t* out, void* check, hipStream_t s);
 // the clustering tool (cluster_kernels.hip): X is [n][d] f64; cen / scl
 // (nullptr: none) are applied as (x - c) / s on load.  cnt[2 d]: per column the
 // non-NaN values, then the +-inf values.  The *_chunks functions size the

@@ -146,6 +146,8 @@ SIGNATURES = {
                                         C.POINTER(_I64), C.POINTER(_I64), _P]),
     "tmh_object_contours": (_I, [_P, _I64, _I, _I, C.POINTER(C.c_int32), _P, _P, _I64, _P, _I64, _P,
                                  _I64, C.POINTER(_I64), C.POINTER(_I64)]),
+    "tmh_polygon_fill_device": (_I, [_P, _P, _P, _P, _I64, _I64, _I, _I, _I64, _I64, _P, _P]),
+    "tmh_polygon_fill": (_I, [_P, _P, _P, _P, _I64, _I64, _I, _I, _I64, _I64, _P]),
     "tmh_column_census_device": (_I, [_P, _I64, _I, _P, _P, _P, _P, _P, _P, _P]),
     "tmh_column_census": (_I, [_P, _I64, _I, _P, _P, _P, _P, _P, _P]),
     "tmh_column_select_device": (_I, [_P, _I64, _I, _P, _P, _I, _P, _P]),
@@ -220,6 +222,10 @@ assert CONTOUR_OBJECT_DTYPE.itemsize == 64
 CONTOUR_LDS_PIXELS = 16384
 CONTOUR_LDS_SMALL_PIXELS = 4096
 CONTOUR_LDS_TINY_PIXELS = 1024
+
+#: TMH_POLYGON_LDS_WORDS: a ring whose clipped bounding box takes more 64-bit words of
+#: bit rows (box height x ceil(box width / 64)) is drawn through memory instead of LDS
+POLYGON_LDS_WORDS = 512
 
 
 #: struct tmh_zchunk (include/tmhip.h): one HDF5 gzip chunk of the input path

@@ -848,11 +848,12 @@ def polygons_of_plane(rows, objects, contours, points, y_offset, x_offset):
 
 class SegmentationImage(Image):
     """A labeled image, one positive int32 identifier per segmented object
-    (tmlib/image.py:696-738).  The reference's ``extract_polygons`` method is
-    the module's function ``extract_polygons(image, y_offset, x_offset)``: the
+    (tmlib/image.py:696-738).  The reference's ``extract_polygons`` method and
+    ``create_from_polygons`` class method are the module's functions
+    ``extract_polygons(image, y_offset, x_offset)`` and
+    ``create_from_polygons(polygons, y_offset, x_offset, dimensions)``: the
     class itself keeps to the attributes tests/test_jterator_cpu.py pins
-    (neither ``extract_polygons`` nor ``create_from_polygons``, which is not
-    built)."""
+    (neither of the two)."""
 
     __slots__ = ()
 
@@ -899,6 +900,79 @@ def extract_polygons(image, y_offset, x_offset):
         raise TypeError('Argument "image" must have type SegmentationImage.')
     rows, objects, contours, points = object_contours(image.array[None])
     return polygons_of_plane(rows[0], objects[0], contours, points, y_offset, x_offset)
+
+
+def polygon_ring(geometry):
+    """The exterior of one geometry of create_from_polygons as int32 [n, 2]
+    global (x, y) pairs: the shell of a ``ContourPolygon``, an [n, 2] integer
+    array, or ``np.array(geometry.exterior.coords).astype(int)`` as the
+    reference takes a shapely polygon's (image.py:769).  Holes are ignored, as
+    there.  An empty ring raises ValueError."""
+    if isinstance(geometry, ContourPolygon):
+        pts = geometry.shell
+    elif hasattr(geometry, "exterior"):
+        pts = np.array(geometry.exterior.coords).astype(int)
+    else:
+        pts = np.asarray(geometry)
+        if pts.dtype.kind not in "iu":
+            raise TypeError("a ring given as an array must have an integer type")
+    if pts.size == 0:
+        raise ValueError("an empty ring")
+    if pts.ndim != 2 or pts.shape[1] != 2:
+        raise ValueError("a ring must be an [n, 2] array of (x, y) pairs")
+    if pts.dtype != np.int32:
+        if pts.min() < -2 ** 31 or pts.max() > 2 ** 31 - 1:
+            raise ValueError("a ring's coordinates must fit 32 bits")
+        pts = pts.astype(np.int32)
+    return np.ascontiguousarray(pts)
+
+
+def label_planes_from_polygons(plane_polygons, y_offset, x_offset, dimensions):
+    """``create_from_polygons`` for many planes in one ``tmh_polygon_fill``
+    call: ``plane_polygons[i]`` is the iterable of (label, geometry) of plane i
+    (geometries as ``polygon_ring`` takes them); returns int32 [n, height,
+    width] with ``dimensions`` = (height, width).  Within a plane a later
+    polygon overwrites an earlier one, as the reference's loop does."""
+    height, width = (int(v) for v in dimensions)
+    if height <= 0 or width <= 0:
+        raise ValueError("dimensions must be positive")
+    rings, planes, labels = [], [], []
+    n_planes = 0
+    for i, polygons in enumerate(plane_polygons):
+        n_planes = i + 1
+        for label, geometry in polygons:
+            label = int(label)
+            if not -2 ** 31 <= label <= 2 ** 31 - 1:
+                raise ValueError("a label must fit int32")
+            rings.append(polygon_ring(geometry))
+            planes.append(i)
+            labels.append(label)
+    out = np.zeros((n_planes, height, width), dtype=np.int32)
+    if n_planes == 0:
+        return out
+    L = hip.lib()
+    first = np.zeros(len(rings) + 1, dtype=np.int64)
+    if rings:
+        np.cumsum([len(r) for r in rings], out=first[1:])
+        points = np.ascontiguousarray(np.concatenate(rings, axis=0))
+    else:
+        points = np.zeros((0, 2), dtype=np.int32)
+    plane = np.asarray(planes, dtype=np.int32)
+    label = np.asarray(labels, dtype=np.int32)
+    hip.check(L.tmh_polygon_fill(hip.ptr(points), hip.ptr(first), hip.ptr(plane), hip.ptr(label),
+                                 len(rings), n_planes, height, width, int(y_offset), int(x_offset),
+                                 hip.ptr(out)))
+    return out
+
+
+def create_from_polygons(polygons, y_offset, x_offset, dimensions, metadata=None):
+    """SegmentationImage.create_from_polygons of the reference
+    (image.py:740-776): the label image of (label, geometry) pairs in global
+    map coordinates, ``y_offset`` / ``x_offset`` subtracted, drawn on the GPU
+    by skimage.draw.polygon's rule.  A module function for
+    the reason ``extract_polygons`` is one."""
+    planes = label_planes_from_polygons([polygons], y_offset, x_offset, dimensions)
+    return SegmentationImage(planes[0], metadata)
 
 
 class IllumstatsImage(Image):

@@ -14,7 +14,13 @@ Differences by design: files are resolved through an ``ExperimentStore``
 ``site_shifts`` / ``site_residues`` as the align step keeps them;
 ``channel_names``: optional name -> channel id, default ``int(name)``).  8-bit
 channels take the existing host path (``tmh_correct_u8`` + ``tmh_align``).
-``objects_input``, running the pipeline and saving its outputs are not built.
+``objects_input`` (api.py:319-339) reads a site's stored outlines from the
+store's optional ``segmentations``: {(name, site_id, tpoint, zplane): [(label,
+ring), ...]} -- what ``MapobjectType.get_segmentations_per_site`` returns, the
+geometries as rings (``image.polygon_ring``) -- and draws all planes of an
+object type in one device call; ``site_offsets``: optional {site_id: (y, x)}
+of ``Site.offset``, default (0, 0).  Running the pipeline and saving its
+outputs are not built.
 """
 from __future__ import annotations
 
@@ -29,6 +35,7 @@ from tmlibrary_amd.metadata import ChannelImageMetadata
 from tmlibrary_amd.models.file import (ExperimentStore, RawChunksUnsupported,
                                        channel_image_shape, read_channel_images)
 from tmlibrary_amd.workflow.align.api import fill_metadata
+from tmlibrary_amd.workflow.jterator.handles import SegmentedObjects
 
 logger = logging.getLogger(__name__)
 
@@ -46,6 +53,26 @@ def site_layout(store, site_id):
             ts.add(info[3])
             zs.add(info[4])
     return len(zs), len(ts)
+
+
+def site_planes(store, site_id):
+    """(sorted z-planes, sorted time points) of ALL files of a site."""
+    zs, ts = set(), set()
+    for info in store.file_info.values():
+        if info[1] == site_id:
+            ts.add(info[3])
+            zs.add(info[4])
+    return sorted(zs), sorted(ts)
+
+
+def aligned_offset(store, site_id):
+    """Site.aligned_offset (tmlib/models/site.py:175-182): the site's offset in
+    the map plus its top and left residue."""
+    y, x = (getattr(store, "site_offsets", None) or {}).get(site_id, (0, 0))
+    res = (getattr(store, "site_residues", None) or {}).get(site_id)
+    if res is None:
+        return int(y), int(x)
+    return int(y) + int(res["top"]), int(x) + int(res["left"])
 
 
 def channel_files(store, site_id, channel_id):
@@ -208,10 +235,29 @@ class ImageAnalysisPipeline(object):
                 corrector.close()
         return out.reshape(n_sites, height, width, n_z, n_t)
 
-    def load_pipeline_inputs(self, site_ids, channels):
+    def _site_objects(self, site_id, name):
+        """api.py:319-339 for one site and object type: the SegmentedObjects
+        with its value drawn from the stored outlines."""
+        zplanes, tpoints = site_planes(self.store, site_id)
+        segmentations = getattr(self.store, "segmentations", None) or {}
+        polygons = [[segmentations.get((name, site_id, t, z), []) for z in zplanes]
+                    for t in tpoints]
+        ids = sorted(f for f, info in self.store.file_info.items() if info[1] == site_id)
+        if not ids:
+            raise ValueError("No image files found for site %r" % (site_id,))
+        H, W, _ = channel_image_shape(self.store.channel_image_file(ids[0]).location)
+        y_offset, x_offset = aligned_offset(self.store, site_id)
+        segm_obj = SegmentedObjects(name, name)
+        segm_obj.add_polygons(polygons, y_offset, x_offset,
+                              aligned_size(self.store, site_id, (H, W)))
+        return segm_obj
+
+    def load_pipeline_inputs(self, site_ids, channels, objects=()):
         """``load_pipeline_input`` for a batch of sites with one stack launch
         per channel; one store dict per site.  The sites must share their
-        aligned size and (n_zplanes, n_tpoints)."""
+        aligned size and (n_zplanes, n_tpoints).  ``objects``: names of object
+        types whose stored outlines become label images (one device call per
+        site and name)."""
         site_ids = list(site_ids)
         logger.info("load pipeline inputs")
         stores = [{"site_id": s, "pipe": dict(), "current_figure": list(), "objects": dict(),
@@ -224,10 +270,16 @@ class ImageAnalysisPipeline(object):
             for k, st in enumerate(stores):
                 # single dimensions removed, as the reference does (api.py:345-346)
                 st["pipe"][name] = np.squeeze(stacks[k])
+        for name in objects:
+            logger.info('load objects "%s"', name)
+            for st in stores:
+                segm_obj = self._site_objects(st["site_id"], name)
+                st["objects"][segm_obj.name] = segm_obj
+                st["pipe"][segm_obj.name] = np.squeeze(segm_obj.value)
         return stores
 
-    def load_pipeline_input(self, site_id, channels):
-        """jterator/api.py:237-348 for ``channels`` = [(name, correct), ...]:
-        {'site_id', 'pipe': {name: array}, 'current_figure', 'objects',
-        'channels'}."""
-        return self.load_pipeline_inputs([site_id], channels)[0]
+    def load_pipeline_input(self, site_id, channels, objects=()):
+        """jterator/api.py:237-348 for ``channels`` = [(name, correct), ...]
+        and ``objects`` = [name, ...]: {'site_id', 'pipe': {name: array},
+        'current_figure', 'objects': {name: SegmentedObjects}, 'channels'}."""
+        return self.load_pipeline_inputs([site_id], channels, objects)[0]
