@@ -8,6 +8,7 @@ correction's +-1 DN carried through clip/scale (<= 1 uint8 step)."""
 import numpy as np
 import pytest
 
+from tmlibrary_amd import hip
 from util import load_golden
 from oracle import corilla_oracle as orc
 
@@ -16,8 +17,16 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def L():
-    from tmlibrary_amd import hip
     return hip.lib()
+
+
+def _chain_on_device(corr, sites, wins, lo, hi):
+    """tmh_correct_chain_u8_device over freshly uploaded sites -> its uint8 sites."""
+    with hip.DeviceBuffer(sites.nbytes) as d_in, hip.DeviceBuffer(sites.size) as d_out:
+        d_in.put(sites)
+        hip.check(hip.lib().tmh_correct_chain_u8_device(corr._h, d_in, d_out, len(sites),
+                                                        hip.ptr(wins), lo, hi, None))
+        return d_out.get(sites.shape, np.uint8)
 
 
 def _md(y=0, x=0, residues=(0, 0, 0, 0)):
@@ -169,8 +178,6 @@ def test_chain_device_random_windows(L, shape, bounds):
     Clip bounds: the usual range, the whole 16-bit range, one wider than the
     old 16,384-entry table limit, and a single-step range (the lone 0 of
     _map_to_uint8) -- all through the 64 KB clip + scale table."""
-    import ctypes as C
-    from tmlibrary_amd import hip
     from tmlibrary_amd.image import Corrector, align_window
     from tmlibrary_amd.synth import synth_sites_host
     H, W = shape
@@ -186,17 +193,7 @@ def test_chain_device_random_windows(L, shape, bounds):
     wins[5]["rows"] = 0  # all padding
     lo, hi = bounds
     corr = Corrector(sm, ss)
-    d_in = C.c_void_p()
-    d_out = C.c_void_p()
-    assert L.tmh_malloc_device(C.byref(d_in), sites.nbytes) == 0
-    assert L.tmh_malloc_device(C.byref(d_out), sites.size) == 0
-    assert L.tmh_memcpy(d_in, sites.ctypes.data, sites.nbytes, 0, None) == 0
-    hip.check(L.tmh_correct_chain_u8_device(corr._h, d_in, d_out, len(sites), hip.ptr(wins), lo,
-                                            hi, None))
-    got = np.empty(sites.shape, np.uint8)
-    assert L.tmh_memcpy(got.ctypes.data, d_out, got.nbytes, 1, None) == 0
-    L.tmh_free_device(d_in)
-    L.tmh_free_device(d_out)
+    got = _chain_on_device(corr, sites, wins, lo, hi)
     corr.close()
     for i, ((y, x), s) in enumerate(zip(shifts, sites)):
         if i == 5:
@@ -215,8 +212,6 @@ def test_chain_overflow_wrap_and_beyond_int32(L, bounds):
     overflow to inf: k_chain_u8t casts without clamping and relies on every
     |value| >= T (T < 2^18) being refined in f64 -- checked here against the
     oracle's x86 cast (oracle/corilla_oracle.py cast_float_to_uint_x86)."""
-    import ctypes as C
-    from tmlibrary_amd import hip
     from tmlibrary_amd.image import Corrector, align_window
     H, W = 64, 320
     rng = np.random.default_rng(5)
@@ -235,16 +230,7 @@ def test_chain_overflow_wrap_and_beyond_int32(L, bounds):
     wins = np.stack([align_window((H, W), y, x, *res, crop=False)[0] for y, x in shifts])
     lo, hi = bounds
     corr = Corrector(mu, sd)
-    d_in, d_out = C.c_void_p(), C.c_void_p()
-    assert L.tmh_malloc_device(C.byref(d_in), sites.nbytes) == 0
-    assert L.tmh_malloc_device(C.byref(d_out), sites.size) == 0
-    assert L.tmh_memcpy(d_in, sites.ctypes.data, sites.nbytes, 0, None) == 0
-    hip.check(L.tmh_correct_chain_u8_device(corr._h, d_in, d_out, len(sites), hip.ptr(wins), lo,
-                                            hi, None))
-    got = np.empty(sites.shape, np.uint8)
-    assert L.tmh_memcpy(got.ctypes.data, d_out, got.nbytes, 1, None) == 0
-    L.tmh_free_device(d_in)
-    L.tmh_free_device(d_out)
+    got = _chain_on_device(corr, sites, wins, lo, hi)
     corr.close()
     # the case mix this test is about, from the oracle's own f64 values
     a = sd.mean() / sd
@@ -266,8 +252,6 @@ def test_chain_without_log_transform(L, bounds):
     -- no zero floor, values may be negative before the x86 cast -- against
     the oracle chain with log_transform=False; one column of tiny std drives
     values past 2^16 and 2^31 (refined in f64)."""
-    import ctypes as C
-    from tmlibrary_amd import hip
     from tmlibrary_amd.image import Corrector, align_window
     from tmlibrary_amd.synth import synth_sites_host
     H, W = 96, 256
@@ -282,16 +266,7 @@ def test_chain_without_log_transform(L, bounds):
     wins = np.stack([align_window((H, W), y, x, *res, crop=False)[0] for y, x in shifts])
     lo, hi = bounds
     corr = Corrector(mu, sd, log_transform=False)
-    d_in, d_out = C.c_void_p(), C.c_void_p()
-    assert L.tmh_malloc_device(C.byref(d_in), sites.nbytes) == 0
-    assert L.tmh_malloc_device(C.byref(d_out), sites.size) == 0
-    assert L.tmh_memcpy(d_in, sites.ctypes.data, sites.nbytes, 0, None) == 0
-    hip.check(L.tmh_correct_chain_u8_device(corr._h, d_in, d_out, len(sites), hip.ptr(wins), lo,
-                                            hi, None))
-    got = np.empty(sites.shape, np.uint8)
-    assert L.tmh_memcpy(got.ctypes.data, d_out, got.nbytes, 1, None) == 0
-    L.tmh_free_device(d_in)
-    L.tmh_free_device(d_out)
+    got = _chain_on_device(corr, sites, wins, lo, hi)
     corr.close()
     for i, ((y, x), s) in enumerate(zip(shifts, sites)):
         want = orc.illuminati_chain(s, mu, sd, (y, x), res, lo, hi, log_transform=False)
@@ -335,40 +310,29 @@ def test_chain_launch_regimes(L, regime_inputs, n_sites):
     one-call output equals, byte for byte, the same sites and windows run 7
     per call (one part each); and the first site of every shift class is
     within 1 of the oracle chain."""
-    import ctypes as C
-    from tmlibrary_amd import hip
     from tmlibrary_amd.image import Corrector
     sm, ss, sites, wins = regime_inputs
     sites, wins = sites[:n_sites], np.ascontiguousarray(wins[:n_sites])
     H, W = sites.shape[1:]
     lo, hi = 100, 3000
     corr = Corrector(sm, ss)
-    d_in, d_out = C.c_void_p(), C.c_void_p()
-    assert L.tmh_malloc_device(C.byref(d_in), sites.nbytes) == 0
-    assert L.tmh_malloc_device(C.byref(d_out), sites.size) == 0
-    assert L.tmh_memcpy(d_in, sites.ctypes.data, sites.nbytes, 0, None) == 0
-
-    def run(s0, n):
-        w = np.ascontiguousarray(wins[s0:s0 + n])
-        hip.check(L.tmh_correct_chain_u8_device(
-            corr._h, C.c_void_p(d_in.value + s0 * H * W * 2), C.c_void_p(d_out.value + s0 * H * W),
-            n, hip.ptr(w), lo, hi, None))
-
-    def fetch():
-        out = np.empty(sites.shape, np.uint8)
-        assert L.tmh_memcpy(out.ctypes.data, d_out, out.nbytes, 1, None) == 0
-        return out
-
     junk = np.full(sites.shape, 0xA5, np.uint8)  # each run must write every byte itself
-    assert L.tmh_memcpy(d_out, junk.ctypes.data, junk.nbytes, 0, None) == 0
-    run(0, n_sites)
-    whole = fetch()
-    assert L.tmh_memcpy(d_out, junk.ctypes.data, junk.nbytes, 0, None) == 0
-    for s0 in range(0, n_sites, 7):
-        run(s0, min(7, n_sites - s0))
-    pieces = fetch()
-    L.tmh_free_device(d_in)
-    L.tmh_free_device(d_out)
+    with hip.DeviceBuffer(sites.nbytes) as d_in, hip.DeviceBuffer(sites.size) as d_out:
+        d_in.put(sites)
+
+        def run(s0, n):
+            w = np.ascontiguousarray(wins[s0:s0 + n])
+            hip.check(L.tmh_correct_chain_u8_device(
+                corr._h, d_in.at(s0 * H * W * 2), d_out.at(s0 * H * W), n, hip.ptr(w), lo, hi,
+                None))
+
+        d_out.put(junk)
+        run(0, n_sites)
+        whole = d_out.get(sites.shape, np.uint8)
+        d_out.put(junk)
+        for s0 in range(0, n_sites, 7):
+            run(s0, min(7, n_sites - s0))
+        pieces = d_out.get(sites.shape, np.uint8)
     corr.close()
     assert np.array_equal(whole, pieces)
     for i, sh in enumerate(_REGIME_SHIFTS):

@@ -12,7 +12,6 @@ decision values agree with ``decision_function(..., 'ovo')`` in libsvm's sign
 within the same bound.  Routes (LDS / memory, one tile / streamed) and repeated
 runs give identical bytes.
 """
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -55,16 +54,15 @@ def forest_device(L, model, X, want_proba=True, skip=0):
     from tmlibrary_amd import hip
     from tmlibrary_amd.tools.base import DeviceTable
     n, c = X.shape[0] - skip, model.classes_.size
-    labels = np.full(n, -1, dtype=np.int32)
-    proba = np.full((n, c), np.nan) if want_proba else None
+    proba = None
     with DeviceTable(X) as t:
         d_labels = t.alloc(4 * n)
         d_proba = t.alloc(8 * n * c) if want_proba else None
-        x = C.c_void_p(t.x.value + 8 * skip * X.shape[1])
+        x = t.x.at(8 * skip * X.shape[1])
         hip.check(L.tmh_forest_predict_device(model.handle(), x, n, d_labels, d_proba, None))
-        hip.check(L.tmh_memcpy(hip.ptr(labels), d_labels, labels.nbytes, 1, None))
+        labels = d_labels.get(n, np.int32)
         if want_proba:
-            hip.check(L.tmh_memcpy(hip.ptr(proba), d_proba, proba.nbytes, 1, None))
+            proba = d_proba.get((n, c), np.float64)
         hip.check(L.tmh_synchronize(None))
     return labels, proba
 
@@ -73,16 +71,15 @@ def svc_device(L, model, X, scaler, want_dec=True):
     from tmlibrary_amd import hip
     from tmlibrary_amd.tools.base import DeviceTable
     n, pairs = X.shape[0], model.rho.size
-    labels = np.full(n, -1, dtype=np.int32)
-    dec = np.full((n, pairs), np.nan) if want_dec else None
+    dec = None
     with DeviceTable(X, scaler) as t:
         d_labels = t.alloc(4 * n)
         d_dec = t.alloc(8 * n * pairs) if want_dec else None
         hip.check(L.tmh_svc_predict_device(model.handle(), t.x, n, t.center, t.scale, d_labels,
                                            d_dec, None))
-        hip.check(L.tmh_memcpy(hip.ptr(labels), d_labels, labels.nbytes, 1, None))
+        labels = d_labels.get(n, np.int32)
         if want_dec:
-            hip.check(L.tmh_memcpy(hip.ptr(dec), d_dec, dec.nbytes, 1, None))
+            dec = d_dec.get((n, pairs), np.float64)
         hip.check(L.tmh_synchronize(None))
     return labels, dec
 
@@ -195,7 +192,7 @@ def test_forest_refusals(L):
         # labels overlapping the probabilities: both are written by one kernel
         assert L.tmh_forest_predict_device(h, t.x, 5, out, out, None) == hip.TMH_EINVAL
         assert b"outputs must not overlap" in L.tmh_last_error()
-        assert L.tmh_forest_predict_device(h, t.x, 5, C.c_void_p(out.value + 16), out, None) \
+        assert L.tmh_forest_predict_device(h, t.x, 5, out.at(16), out, None) \
             == hip.TMH_EINVAL
         assert L.tmh_forest_predict_device(h, t.x, 0, out, None, None) == hip.TMH_EINVAL
         assert L.tmh_forest_predict_device(h, t.x, 2 ** 31, out, None, None) == hip.TMH_EINVAL

@@ -361,11 +361,8 @@ def test_refusals_launch_no_kmeans_kernel(L):
         with pytest.raises(ValueError, match="NaN"):
             good.predict(bad)
         # overlapping buffers (device forms)
-        dev = C.c_void_p()
-        hip.check(L.tmh_malloc_device(C.byref(dev), X.nbytes))
-        try:
-            hip.check(L.tmh_memcpy(dev, hip.ptr(X), X.nbytes, 0, None))
-            inside = C.c_void_p(dev.value + 64)
+        with hip.DeviceBuffer.from_array(X) as dev:
+            inside = dev.at(64)
             assert L.tmh_kmeans_fit_device(dev, 300, 4, 3, None, None, hip.ptr(C0), 10, 1e-4,
                                            hip.ptr(out_c), inside, C.byref(inertia),
                                            C.byref(n_iter), C.byref(tol_abs),
@@ -377,17 +374,10 @@ def test_refusals_launch_no_kmeans_kernel(L):
             cs = np.ones(4)
             assert L.tmh_robust_scale(hip.ptr(X), 300, 4, hip.ptr(cs), hip.ptr(cs),
                                       hip.ptr(X)) == hip.TMH_OK   # host form: staged, no aliasing
-            dcs = C.c_void_p()
-            hip.check(L.tmh_malloc_device(C.byref(dcs), cs.nbytes))
-            try:
-                hip.check(L.tmh_memcpy(dcs, hip.ptr(cs), cs.nbytes, 0, None))
+            with hip.DeviceBuffer.from_array(cs) as dcs:
                 assert L.tmh_robust_scale_device(dev, 300, 4, dcs, dcs, inside,
                                                  None) == hip.TMH_EINVAL
                 assert b"overlap" in L.tmh_last_error()
-            finally:
-                L.tmh_free_device(dcs)
-        finally:
-            L.tmh_free_device(dev)
         for kernel in ("kmeans_assign", "kmeans_update", "kmeans_seed"):
             assert launches(L, kernel) == 0, kernel
     finally:

@@ -9,6 +9,7 @@ the kernel's streams are the bytes of the host build of the same core
 through the GPU encoder read back through libhdf5 and through the GPU reader;
 the z projection equals numpy; the imextract job runs end to end.
 """
+import contextlib
 import ctypes as C
 import types
 import zlib
@@ -17,20 +18,19 @@ import numpy as np
 import pytest
 
 import deflate_cases as dc
+from tmlibrary_amd import hip
+from util import keep  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def L():
-    from tmlibrary_amd import hip
     return hip.lib()
 
 
 def _deflate(L, raws):
     """tmh_deflate_device over the byte strings as one launch: (streams, statuses)."""
-    from tmlibrary_amd import hip
-    from test_gpu_parity import Dev
     n = len(raws)
     tab = np.zeros(n, hip.ZCHUNK_DTYPE)
     roff = 0
@@ -40,21 +40,21 @@ def _deflate(L, raws):
     raw_max = int(tab["raw_len"].max())
     dst_bytes = n * int(L.tmh_deflate_bound(raw_max))
     scr = int(L.tmh_deflate_scratch_bytes(n, raw_max))
-    d_raw, d_tab, d_dst = Dev(L, max(roff, 1)), Dev(L, tab.nbytes), Dev(L, dst_bytes)
-    d_scr, d_st, d_tot = Dev(L, scr), Dev(L, 4 * n), Dev(L, 8)
-    d_raw.put(np.frombuffer(b"".join(raws), np.uint8))
-    d_tab.put(tab)
-    hip.check(L.tmh_deflate_device(d_raw.p, roff, d_tab.p, n, raw_max, d_dst.p, dst_bytes,
-                                   d_scr.p, scr, d_st.p, d_tot.p, None))
-    assert L.tmh_synchronize(None) == 0
-    total = int(d_tot.get(np.int64, (1,))[0])
-    tab = d_tab.get(hip.ZCHUNK_DTYPE, (n,))
-    st = d_st.get(np.int32, (n,))
-    blob = d_dst.get(np.uint8, (max(total, 1),))
-    assert total == int(tab["src_len"].sum())
-    assert np.array_equal(tab["src_off"], np.concatenate([[0], np.cumsum(tab["src_len"])[:-1]]))
-    for b in (d_raw, d_tab, d_dst, d_scr, d_st, d_tot):
-        b.free()
+    with contextlib.ExitStack() as stack:
+        keep = stack.enter_context
+        sizes = (max(roff, 1), tab.nbytes, dst_bytes, max(scr, 1), 4 * n, 8)
+        d_raw, d_tab, d_dst, d_scr, d_st, d_tot = [keep(hip.DeviceBuffer(b)) for b in sizes]
+        d_raw.put(np.frombuffer(b"".join(raws), np.uint8))
+        d_tab.put(tab)
+        hip.check(L.tmh_deflate_device(d_raw, roff, d_tab, n, raw_max, d_dst, dst_bytes,
+                                       d_scr, scr, d_st, d_tot, None))
+        assert L.tmh_synchronize(None) == 0
+        total = int(d_tot.get((1,), np.int64)[0])
+        tab = d_tab.get((n,), hip.ZCHUNK_DTYPE)
+        st = d_st.get((n,), np.int32)
+        blob = d_dst.get((max(total, 1),), np.uint8)
+        assert total == int(tab["src_len"].sum())
+        assert np.array_equal(tab["src_off"], np.concatenate([[0], np.cumsum(tab["src_len"])[:-1]]))
     return [blob[t["src_off"]:t["src_off"] + t["src_len"]].tobytes() for t in tab], st
 
 
@@ -71,31 +71,27 @@ def test_device_bytes_equal_host_core(L, tmp_path):
         assert len(s) <= dc.bound(len(raw)), name
 
 
-def test_bad_table_entry_is_reported(L):
-    from tmlibrary_amd import hip
-    from test_gpu_parity import Dev
+def test_bad_table_entry_is_reported(L, keep):
     raw = bytes(range(200))
     tab = np.zeros(2, hip.ZCHUNK_DTYPE)
     tab[0] = (0, 0, 0, 200, 0, 0, 0, 0, 0)
     tab[1] = (0, 0, 100, 200, 1, 0, 0, 0, 0)  # runs past the raw buffer
     dst_bytes = 2 * int(L.tmh_deflate_bound(200))
     scr = int(L.tmh_deflate_scratch_bytes(2, 200))
-    bufs = [Dev(L, 200), Dev(L, tab.nbytes), Dev(L, dst_bytes), Dev(L, scr), Dev(L, 8), Dev(L, 8)]
-    d_raw, d_tab, d_dst, d_scr, d_st, d_tot = bufs
+    sizes = (200, tab.nbytes, dst_bytes, max(scr, 1), 8, 8)
+    d_raw, d_tab, d_dst, d_scr, d_st, d_tot = [keep(hip.DeviceBuffer(b)) for b in sizes]
     d_raw.put(np.frombuffer(raw, np.uint8))
     d_tab.put(tab)
-    hip.check(L.tmh_deflate_device(d_raw.p, 200, d_tab.p, 2, 200, d_dst.p, dst_bytes, d_scr.p, scr,
-                                   d_st.p, d_tot.p, None))
+    hip.check(L.tmh_deflate_device(d_raw, 200, d_tab, 2, 200, d_dst, dst_bytes, d_scr, scr,
+                                   d_st, d_tot, None))
     assert L.tmh_synchronize(None) == 0
-    st = d_st.get(np.int32, (2,))
-    tab = d_tab.get(hip.ZCHUNK_DTYPE, (2,))
-    total = int(d_tot.get(np.int64, (1,))[0])
+    st = d_st.get((2,), np.int32)
+    tab = d_tab.get((2,), hip.ZCHUNK_DTYPE)
+    total = int(d_tot.get((1,), np.int64)[0])
     assert st[0] == 0 and st[1] == 6 and tab["src_len"][1] == 0 and total == tab["src_len"][0]
-    assert zlib.decompress(d_dst.get(np.uint8, (total,)).tobytes()) == raw
-    assert L.tmh_deflate_device(d_raw.p, 200, d_tab.p, 2, 200, d_dst.p, dst_bytes - 1, d_scr.p, scr,
-                                d_st.p, d_tot.p, None) == hip.TMH_EINVAL
-    for b in bufs:
-        b.free()
+    assert zlib.decompress(d_dst.get((total,), np.uint8).tobytes()) == raw
+    assert L.tmh_deflate_device(d_raw, 200, d_tab, 2, 200, d_dst, dst_bytes - 1, d_scr, scr,
+                                d_st, d_tot, None) == hip.TMH_EINVAL
 
 
 @pytest.mark.parametrize("n,H,W,dtype,chunks", [
@@ -104,11 +100,9 @@ def test_bad_table_entry_is_reported(L):
     (2, 20, 30, np.uint8, (20, 30)),
     (1, 1, 1, np.uint16, (1, 1)),
 ])
-def test_device_round_trip(L, n, H, W, dtype, chunks):
+def test_device_round_trip(L, keep, n, H, W, dtype, chunks):
     """gather -> deflate -> inflate -> place returns the images bit for bit."""
-    from tmlibrary_amd import hip
     from tmlibrary_amd.synth import synth_exact_sites_host
-    from test_gpu_parity import Dev
     es = np.dtype(dtype).itemsize
     if H * W == 1:
         imgs = np.full((n, 1, 1), 0xBEEF, np.uint16)
@@ -122,37 +116,35 @@ def test_device_round_trip(L, n, H, W, dtype, chunks):
     dst_bytes = nch * int(L.tmh_deflate_bound(raw_max))
     scr = max(int(L.tmh_deflate_scratch_bytes(nch, raw_max)),
               int(L.tmh_inflate_scratch_bytes(nch, raw_max)))
-    d_img, d_out = Dev(L, imgs.nbytes), Dev(L, imgs.nbytes)
-    d_tab, d_raw, d_raw2 = Dev(L, nch * hip.ZCHUNK_DTYPE.itemsize), Dev(L, raw_bytes), Dev(L, raw_bytes)
-    d_dst, d_scr, d_st, d_tot = Dev(L, dst_bytes + 16), Dev(L, scr), Dev(L, 4 * nch), Dev(L, 8)
-    bufs = [d_img, d_out, d_tab, d_raw, d_raw2, d_dst, d_scr, d_st, d_tot]
+    sizes = (imgs.nbytes, imgs.nbytes, nch * hip.ZCHUNK_DTYPE.itemsize, raw_bytes, raw_bytes,
+             dst_bytes + 16, max(scr, 1), 4 * nch, 8)
+    d_img, d_out, d_tab, d_raw, d_raw2, d_dst, d_scr, d_st, d_tot = \
+        [keep(hip.DeviceBuffer(b)) for b in sizes]
     d_img.put(imgs)
     d_out.put(np.full(imgs.shape, 0xA5, dtype))
-    hip.check(L.tmh_gather_chunks_device(d_img.p, n, H, W, es, cr, cc, d_tab.p, d_raw.p, None))
-    hip.check(L.tmh_deflate_device(d_raw.p, raw_bytes, d_tab.p, nch, raw_max, d_dst.p, dst_bytes,
-                                   d_scr.p, scr, d_st.p, d_tot.p, None))
+    hip.check(L.tmh_gather_chunks_device(d_img, n, H, W, es, cr, cc, d_tab, d_raw, None))
+    hip.check(L.tmh_deflate_device(d_raw, raw_bytes, d_tab, nch, raw_max, d_dst, dst_bytes,
+                                   d_scr, scr, d_st, d_tot, None))
     assert L.tmh_synchronize(None) == 0
-    assert not np.any(d_st.get(np.int32, (nch,)))
-    total = int(d_tot.get(np.int64, (1,))[0])
-    tab = d_tab.get(hip.ZCHUNK_DTYPE, (nch,))
+    assert not np.any(d_st.get((nch,), np.int32))
+    total = int(d_tot.get((1,), np.int64)[0])
+    tab = d_tab.get((nch,), hip.ZCHUNK_DTYPE)
     assert np.array_equal(tab["image"], np.repeat(np.arange(n), nch // n))
     assert np.all(tab["raw_len"] == raw_max) and tab["row0"].max() < H and tab["col0"].max() < W
     # the gathered chunks are HDF5's: zero padded past the extent
-    raw = d_raw.get(np.uint8, (raw_bytes,)).tobytes()
+    raw = d_raw.get((raw_bytes,), np.uint8).tobytes()
     want = b"".join(c for img in imgs for c in dc.chunkify(img, cr, cc))
     assert raw == want
-    blob = d_dst.get(np.uint8, (max(total, 1),))
+    blob = d_dst.get((max(total, 1),), np.uint8)
     for t in tab[:: max(1, nch // 16)]:  # zlib takes them too
         assert zlib.decompress(blob[t["src_off"]:t["src_off"] + t["src_len"]].tobytes()) == \
             raw[t["raw_off"]:t["raw_off"] + t["raw_len"]]
-    hip.check(L.tmh_inflate_device(d_dst.p, total, d_tab.p, nch, raw_max, d_raw2.p, raw_bytes,
-                                   d_scr.p, scr, d_st.p, None))
-    hip.check(L.tmh_place_chunks_device(d_raw2.p, d_tab.p, nch, H, W, es, cr, cc, d_out.p, None))
+    hip.check(L.tmh_inflate_device(d_dst, total, d_tab, nch, raw_max, d_raw2, raw_bytes,
+                                   d_scr, scr, d_st, None))
+    hip.check(L.tmh_place_chunks_device(d_raw2, d_tab, nch, H, W, es, cr, cc, d_out, None))
     assert L.tmh_synchronize(None) == 0
-    assert not np.any(d_st.get(np.int32, (nch,)))
-    assert np.array_equal(d_out.get(dtype, imgs.shape), imgs)
-    for b in bufs:
-        b.free()
+    assert not np.any(d_st.get((nch,), np.int32))
+    assert np.array_equal(d_out.get(imgs.shape, dtype), imgs)
 
 
 @pytest.mark.parametrize("H,W,dtype,chunks", [(300, 500, np.uint16, None),
@@ -193,7 +185,6 @@ def test_files_written_by_the_device_encoder(L, tmp_path, monkeypatch, H, W, dty
 @pytest.mark.parametrize("dtype", [np.uint8, np.uint16])
 @pytest.mark.parametrize("z", [1, 2, 5])
 def test_zproject_max_small(L, dtype, z):
-    from tmlibrary_amd import hip
     rng = np.random.default_rng(z)
     planes = rng.integers(0, np.iinfo(dtype).max, (3, z, 37, 53)).astype(dtype)
     out = np.empty((3, 37, 53), dtype)
@@ -203,7 +194,6 @@ def test_zproject_max_small(L, dtype, z):
 
 
 def test_zproject_max_fullsize(L):
-    from tmlibrary_amd import hip
     rng = np.random.default_rng(11)
     planes = rng.integers(0, 65536, (1, 3, 2160, 2560), dtype=np.uint16)
     out = np.empty((1, 2160, 2560), np.uint16)
@@ -216,7 +206,6 @@ def test_zproject_max_fullsize(L):
 
 
 def test_host_wrapper_deflate_images(L):
-    from tmlibrary_amd import hip
     from tmlibrary_amd.synth import synth_exact_sites_host
     imgs = synth_exact_sites_host(2, 37, 53)
     n = 2 * 3 * 4

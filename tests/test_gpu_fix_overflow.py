@@ -15,6 +15,7 @@ corrected values), |byte difference| <= 1 (the chain's uint8).
 Input and output of the device entry points must not overlap (the fixups
 re-read the input): the last tests check that such calls are refused.
 """
+import contextlib
 import ctypes as C
 import functools
 
@@ -24,8 +25,8 @@ import pytest
 import overflow_cases as oc
 from oracle import corilla_oracle as orc
 from test_gpu_fullsize import _results, _stats_handle
-from test_gpu_parity import Dev
-from util import assert_dn, dn_report
+from tmlibrary_amd import hip
+from util import assert_dn, dn_report, keep  # noqa: F401 (keep: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -34,7 +35,6 @@ Q = 100000
 
 @pytest.fixture(scope="module")
 def L():
-    from tmlibrary_amd import hip
     return hip.lib()
 
 
@@ -57,26 +57,24 @@ PLAIN = {"log": oc.plain_log, "nolog": oc.plain_nolog, "scalar": lambda: oc.plai
 
 @pytest.mark.parametrize("name,clip", [("log", None), ("log", (1000, 60000)), ("nolog", None),
                                        ("nolog", (1000, 60000)), ("scalar", None)])
-def test_plain_u16_list_overflow(L, name, clip):
+def test_plain_u16_list_overflow(L, keep, name, clip):
     """k_fix_correct<LOG, uint16_t, 16> (apply_kernels.hip) in all mode after
     k_correct_u16_vec8 (512 x 512) or k_correct_scalar (511 x 513: npx % 8 ==
     7, so every site's last group of the all-mode walk is partial and its
     p >= npx guard decides): 1.3 M flagged pixels of 5 sites against 2**20
     entries, 88 % of them wrong if left unrefined (check_pixel_overflow)."""
-    from tmlibrary_amd import hip
     case = PLAIN[name]()
     print(oc.check_pixel_overflow(case, clip))
     assert (case.npx % 8 == 7) == (name == "scalar")
     corr = new_corrector(case)
-    d_in, d_out = Dev(L, case.sites.nbytes), Dev(L, case.sites.nbytes)
+    d_in = keep(hip.DeviceBuffer(case.sites.nbytes))
+    d_out = keep(hip.DeviceBuffer(case.sites.nbytes))
     d_in.put(case.sites)
     d_out.put(np.full(case.sites.shape, 0xA5A5, np.uint16))
     lo, hi = clip or (-1, -1)
-    hip.check(L.tmh_correct_u16_device(corr._h, d_in.p, d_out.p, case.n, lo, hi, None))
+    hip.check(L.tmh_correct_u16_device(corr._h, d_in, d_out, case.n, lo, hi, None))
     assert L.tmh_synchronize(None) == 0
-    got = d_out.get(np.uint16, case.sites.shape)
-    d_in.free()
-    d_out.free()
+    got = d_out.get(case.sites.shape, np.uint16)
     corr.close()
     want = case.want() if clip is None else np.clip(case.want(), *clip)
     report(name, got, want)
@@ -115,59 +113,57 @@ def fused_jobs(L, jobs, mode):
     table) or "multi" (tmh_correct_u16_hist_multi_device).  Returns per job
     (corrected sites, per-site histograms, pooled histogram, percentile sums,
     the configuration that ran)."""
-    from tmlibrary_amd import hip
     from tmlibrary_amd.image import ZERO_LOG10
-    st, bufs = [], []
-    for case, cfg in jobs:
-        h = _stats_handle(L, case.H, case.W, hip.TMH_STATS_KEEP_SITE_HIST)
-        hip.check(L.tmh_stats_set_option(h, hip.TMH_OPT_FUSED_CONFIG, cfg))
-        d_in, d_out = Dev(L, case.sites.nbytes), Dev(L, case.sites.nbytes)
-        mean, std = Dev(L, case.npx * 8), Dev(L, case.npx * 8)
-        d_in.put(case.sites)
-        d_out.put(np.full(case.sites.shape, 0xA5A5, np.uint16))
-        mean.put(case.mean)
-        std.put(case.std)
-        c = C.c_void_p()
-        hip.check(L.tmh_corrector_create_device(mean.p, std.p, case.H, case.W, 1, ZERO_LOG10, None,
-                                                C.byref(c)))
-        hip.check(L.tmh_stats_update_welford_device(h, d_in.p, case.n, 1, None))
+    with contextlib.ExitStack() as stack:
+        keep = stack.enter_context
+        st = []
+        for case, cfg in jobs:
+            h = _stats_handle(L, case.H, case.W, hip.TMH_STATS_KEEP_SITE_HIST)
+            hip.check(L.tmh_stats_set_option(h, hip.TMH_OPT_FUSED_CONFIG, cfg))
+            d_in = keep(hip.DeviceBuffer(case.sites.nbytes))
+            d_out = keep(hip.DeviceBuffer(case.sites.nbytes))
+            mean, std = keep(hip.DeviceBuffer(case.npx * 8)), keep(hip.DeviceBuffer(case.npx * 8))
+            d_in.put(case.sites)
+            d_out.put(np.full(case.sites.shape, 0xA5A5, np.uint16))
+            mean.put(case.mean)
+            std.put(case.std)
+            c = C.c_void_p()
+            hip.check(L.tmh_corrector_create_device(mean, std, case.H, case.W, 1, ZERO_LOG10, None,
+                                                    C.byref(c)))
+            hip.check(L.tmh_stats_update_welford_device(h, d_in, case.n, 1, None))
+            assert L.tmh_synchronize(None) == 0
+            st.append((h, c, d_in, d_out))
+        if mode == "multi":
+            n = len(jobs)
+            arr = lambda xs: (C.c_void_p * n)(*[C.c_void_p(x) for x in xs])  # noqa: E731
+            hip.check(L.tmh_correct_u16_hist_multi_device(
+                arr([s[1].value for s in st]), arr([s[0].value for s in st]), n,
+                arr([s[2].ptr.value for s in st]), arr([s[3].ptr.value for s in st]),
+                (C.c_int64 * n)(*[case.n for case, _ in jobs]), -1, -1, None))
+        for (case, _), (h, c, d_in, d_out) in zip(jobs, st):
+            if mode == "single":
+                hip.check(L.tmh_correct_u16_hist_device(c, h, d_in, d_out, case.n, -1, -1, None))
+            elif mode == "blocks":  # blocks of 4 sites (the smallest): the sites fill part of one
+                assert case.n <= 4
+                t_in, t_out = keep(hip.DeviceBuffer(8)), keep(hip.DeviceBuffer(8))
+                t_in.put(np.array([d_in.ptr.value], np.int64))
+                t_out.put(np.array([d_out.ptr.value], np.int64))
+                hip.check(L.tmh_correct_u16_hist_blocks_device(c, h, t_in, t_out, 2, case.n, -1, -1,
+                                                               None))
         assert L.tmh_synchronize(None) == 0
-        st.append((h, c, d_in, d_out))
-        bufs += [d_in, d_out, mean, std]
-    if mode == "multi":
-        n = len(jobs)
-        arr = lambda xs: (C.c_void_p * n)(*[C.c_void_p(x) for x in xs])  # noqa: E731
-        hip.check(L.tmh_correct_u16_hist_multi_device(
-            arr([s[1].value for s in st]), arr([s[0].value for s in st]), n,
-            arr([s[2].p.value for s in st]), arr([s[3].p.value for s in st]),
-            (C.c_int64 * n)(*[case.n for case, _ in jobs]), -1, -1, None))
-    for (case, _), (h, c, d_in, d_out) in zip(jobs, st):
-        if mode == "single":
-            hip.check(L.tmh_correct_u16_hist_device(c, h, d_in.p, d_out.p, case.n, -1, -1, None))
-        elif mode == "blocks":  # blocks of 4 sites (the smallest): the sites fill part of one
-            assert case.n <= 4
-            t_in, t_out = Dev(L, 8), Dev(L, 8)
-            t_in.put(np.array([d_in.p.value], np.int64))
-            t_out.put(np.array([d_out.p.value], np.int64))
-            bufs += [t_in, t_out]
-            hip.check(L.tmh_correct_u16_hist_blocks_device(c, h, t_in.p, t_out.p, 2, case.n, -1, -1,
-                                                           None))
-    assert L.tmh_synchronize(None) == 0
-    res = []
-    for (case, _), (h, c, d_in, d_out) in zip(jobs, st):
-        r = _results(L, h, case.H, case.W, case.n, Q)
-        sh = []
-        for i in range(case.n):
-            x = np.empty(65536, np.uint32)
-            hip.check(L.tmh_stats_site_histogram(h, i, hip.ptr(x)))
-            sh.append(x.astype(np.uint64))
-        fc = C.c_int()
-        hip.check(L.tmh_stats_job_choice(h, None, None, C.byref(fc)))
-        res.append((d_out.get(np.uint16, case.sites.shape), sh, r["hist"], r["acc"], fc.value))
-        L.tmh_corrector_destroy(c)
-        L.tmh_stats_destroy(h)
-    for b in bufs:
-        b.free()
+        res = []
+        for (case, _), (h, c, d_in, d_out) in zip(jobs, st):
+            r = _results(L, h, case.H, case.W, case.n, Q)
+            sh = []
+            for i in range(case.n):
+                x = np.empty(65536, np.uint32)
+                hip.check(L.tmh_stats_site_histogram(h, i, hip.ptr(x)))
+                sh.append(x.astype(np.uint64))
+            fc = C.c_int()
+            hip.check(L.tmh_stats_job_choice(h, None, None, C.byref(fc)))
+            res.append((d_out.get(case.sites.shape, np.uint16), sh, r["hist"], r["acc"], fc.value))
+            L.tmh_corrector_destroy(c)
+            L.tmh_stats_destroy(h)
     return res
 
 
@@ -219,28 +215,25 @@ def test_fused_overflow_next_to_an_ordinary_job(L):
 
 
 @pytest.mark.parametrize("bounds", [(100, 3000), (0, 65535)])
-def test_chain_list_overflow(L, bounds):
+def test_chain_list_overflow(L, keep, bounds):
     """k_fix_chain (chain_kernels.hip) in all mode after k_chain_u8t: 2 sites of
     2160 x 2560, one unshifted and one shifted by (2, -3), more flagged groups
     inside the source windows alone than the list holds (check_chain_overflow).
     All mode walks every source pixel and must map each through the site's
     window and leave the padding alone: the bytes outside the destination
     window equal the oracle's exactly, the rest within 1."""
-    from tmlibrary_amd import hip
     case = oc.full_size()
     cond, wins = oc.check_chain_overflow(case, bounds)
     print(cond)
     corr = new_corrector(case)
-    d_in, d_out = Dev(L, case.sites.nbytes), Dev(L, case.sites.size)
+    d_in, d_out = keep(hip.DeviceBuffer(case.sites.nbytes)), keep(hip.DeviceBuffer(case.sites.size))
     d_in.put(case.sites)
     d_out.put(np.full(case.sites.shape, 0xA5, np.uint8))
     wins = np.ascontiguousarray(wins)
-    hip.check(L.tmh_correct_chain_u8_device(corr._h, d_in.p, d_out.p, case.n, hip.ptr(wins),
+    hip.check(L.tmh_correct_chain_u8_device(corr._h, d_in, d_out, case.n, hip.ptr(wins),
                                             bounds[0], bounds[1], None))
     assert L.tmh_synchronize(None) == 0
-    got = d_out.get(np.uint8, case.sites.shape)
-    d_in.free()
-    d_out.free()
+    got = d_out.get(case.sites.shape, np.uint8)
     corr.close()
     for i, (shift, w) in enumerate(zip(oc.CHAIN_SHIFTS, wins)):
         want = orc.illuminati_chain(case.sites[i], case.mean, case.std, shift, oc.CHAIN_RESIDUES,
@@ -268,7 +261,6 @@ def test_stack_list_overflow(L):
     import torch
 
     from test_gpu_jterator import expected_stack
-    from tmlibrary_amd import hip
     case = oc.plain_log()
     print(oc.check_stack_overflow(case))
     site, slot, win = oc.stack_layout()
@@ -335,14 +327,13 @@ def test_fused_unit_set_overflow(L):
 # ---- E: input and output must not overlap ----------------------------------------------
 
 def _refused(L, rc):
-    from tmlibrary_amd import hip
     assert rc == hip.TMH_EINVAL
     msg = L.tmh_last_error().decode()
     assert "input and output" in msg and "must not overlap" in msg, msg
     assert L.tmh_synchronize(None) == 0
 
 
-def test_correct_u16_device_refuses_overlap(L):
+def test_correct_u16_device_refuses_overlap(L, keep):
     """tmh_correct_u16_device (abi_apply.hip): k_fix_correct re-reads the input
     after the streaming kernel stored the output, so an in-place call would be
     wrong on every flagged pixel.  In place and offset by one site either way:
@@ -351,23 +342,22 @@ def test_correct_u16_device_refuses_overlap(L):
     mean, std = oc.recipe_planes(H, W, 71, big_rows=(H // 2,))
     case = oc.Case(oc.uniform_sites(n + 1, H, W, 72, 20000, 65535), mean, std)
     corr = new_corrector(case)
-    buf = Dev(L, case.sites.nbytes)
+    buf = keep(hip.DeviceBuffer(case.sites.nbytes))
     buf.put(case.sites)
-    at = lambda k: C.c_void_p(buf.p.value + 2 * k * case.npx)  # noqa: E731
+    at = lambda k: buf.at(2 * k * case.npx)  # noqa: E731
     for i, o in ((0, 0), (0, 1), (1, 0)):
         _refused(L, L.tmh_correct_u16_device(corr._h, at(i), at(o), n, -1, -1, None))
-        assert np.array_equal(buf.get(np.uint16, case.sites.shape), case.sites)
+        assert np.array_equal(buf.get(case.sites.shape, np.uint16), case.sites)
     # adjacent runs do not overlap
     assert L.tmh_correct_u16_device(corr._h, at(0), at(1), 1, -1, -1, None) == 0
     assert L.tmh_synchronize(None) == 0
-    got = buf.get(np.uint16, case.sites.shape)
+    got = buf.get(case.sites.shape, np.uint16)
     assert_dn(got[1], case.want()[0])
     assert np.array_equal(got[0], case.sites[0]) and np.array_equal(got[2], case.sites[2])
-    buf.free()
     corr.close()
 
 
-def test_correct_stack_device_refuses_overlap(L):
+def test_correct_stack_device_refuses_overlap(L, keep):
     """tmh_correct_stack_u16_device (abi_chain.hip): k_fix_stack re-reads the
     planes.  The stack written over its own planes, and starting one plane in:
     TMH_EINVAL, nothing written."""
@@ -375,16 +365,14 @@ def test_correct_stack_device_refuses_overlap(L):
     mean, std = oc.recipe_planes(H, W, 73, big_rows=(H // 2,))
     case = oc.Case(oc.uniform_sites(3, H, W, 74, 20000, 65535), mean, std)
     corr = new_corrector(case)
-    from tmlibrary_amd import hip
     site, slot = np.array([0, 0], np.int32), np.array([0, 1], np.int32)
     win = np.zeros(2, dtype=hip.WINDOW_DTYPE)
     win["src_r0"], win["src_c0"], win["rows"], win["cols"] = 2, 3, 60, 60
-    buf = Dev(L, case.sites.nbytes)
+    buf = keep(hip.DeviceBuffer(case.sites.nbytes))
     buf.put(case.sites)
     for o in (0, 1):  # 2 planes in, 60 x 60 x 2 values out: inside 2 planes' room
-        out = C.c_void_p(buf.p.value + 2 * o * case.npx)
-        _refused(L, L.tmh_correct_stack_u16_device(corr._h, buf.p, out, 2, H, W, hip.ptr(site),
+        out = buf.at(2 * o * case.npx)
+        _refused(L, L.tmh_correct_stack_u16_device(corr._h, buf, out, 2, H, W, hip.ptr(site),
                                                    hip.ptr(slot), hip.ptr(win), 1, 2, 60, 60, None))
-        assert np.array_equal(buf.get(np.uint16, case.sites.shape), case.sites)
-    buf.free()
+        assert np.array_equal(buf.get(case.sites.shape, np.uint16), case.sites)
     corr.close()

@@ -30,15 +30,15 @@ import numpy as np
 import pytest
 
 from oracle import corilla_oracle as orc
-from test_gpu_parity import Dev, check_order_stats, site_order_stats
-from util import assert_close_rel, dn_report
+from test_gpu_parity import check_order_stats, site_order_stats
+from tmlibrary_amd import hip
+from util import assert_close_rel, dn_report, keep  # noqa: F401 (keep: a fixture)
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def L():
-    from tmlibrary_amd import hip
     return hip.lib()
 
 
@@ -49,7 +49,6 @@ def _tables(H, W, Q=100000):
 
 
 def _stats_handle(L, H, W, flags):
-    from tmlibrary_amd import hip
     lo, hi, gamma, lut = _tables(H, W)
     h = C.c_void_p()
     hip.check(L.tmh_stats_create(H, W, len(lo), hip.ptr(lo), hip.ptr(hi), hip.ptr(gamma),
@@ -58,7 +57,6 @@ def _stats_handle(L, H, W, flags):
 
 
 def _results(L, h, H, W, n_sites, Q=100000):
-    from tmlibrary_amd import hip
     nn = C.c_int64()
     mean = np.empty((H, W))
     std = np.empty((H, W))
@@ -70,10 +68,9 @@ def _results(L, h, H, W, n_sites, Q=100000):
 
 
 @pytest.mark.timeout(900)
-def test_headline_pipeline_fullsize(L):
+def test_headline_pipeline_fullsize(L, keep):
     import torch
 
-    from tmlibrary_amd import hip
     from tmlibrary_amd.image import ZERO_LOG10
     from tmlibrary_amd.synth import synth_exact_host
     H, W, N = 2160, 2560, 128
@@ -82,29 +79,29 @@ def test_headline_pipeline_fullsize(L):
     dev = torch.device("cuda", 0)
     stream = torch.cuda.Stream(dev)
     sp = C.c_void_p(stream.cuda_stream)
-    d_in, d_out = Dev(L, N * npx * 2), Dev(L, N * npx * 2)
-    planes = [Dev(L, npx * 8) for _ in range(5)]
+    d_in, d_out = keep(hip.DeviceBuffer(N * npx * 2)), keep(hip.DeviceBuffer(N * npx * 2))
+    planes = [keep(hip.DeviceBuffer(npx * 8)) for _ in range(5)]
     mean, std, smean, sstd, tmp = planes
-    hip.check(L.tmh_synth_sites_device(d_in.p, N, H, W, seed, channel, first,
+    hip.check(L.tmh_synth_sites_device(d_in, N, H, W, seed, channel, first,
                                        hip.TMH_SYNTH_STANDARD, sp))
     h = _stats_handle(L, H, W, hip.TMH_STATS_KEEP_SITE_HIST)
     hip.check(L.tmh_stats_set_stream(h, sp))
     c = C.c_void_p()
     L.tmh_synchronize(None)
-    hip.check(L.tmh_corrector_create_device(mean.p, std.p, H, W, 1, ZERO_LOG10, sp, C.byref(c)))
+    hip.check(L.tmh_corrector_create_device(mean, std, H, W, 1, ZERO_LOG10, sp, C.byref(c)))
 
     def job():  # bench.py Channel.stats() + Channel.apply(), same calls, same stream
         hip.check(L.tmh_stats_reset(h))
-        hip.check(L.tmh_stats_update_welford_device(h, d_in.p, N, 1, sp))
-        hip.check(L.tmh_stats_finalize_device(h, mean.p, std.p, sp))
-        hip.check(L.tmh_smooth_f64_device(mean.p, smean.p, tmp.p, H, W, 5.0, sp))
-        hip.check(L.tmh_smooth_f64_device(std.p, sstd.p, tmp.p, H, W, 5.0, sp))
-        hip.check(L.tmh_corrector_update_device(c, smean.p, sstd.p, sp))
-        hip.check(L.tmh_correct_u16_hist_device(c, h, d_in.p, d_out.p, N, -1, -1, sp))
+        hip.check(L.tmh_stats_update_welford_device(h, d_in, N, 1, sp))
+        hip.check(L.tmh_stats_finalize_device(h, mean, std, sp))
+        hip.check(L.tmh_smooth_f64_device(mean, smean, tmp, H, W, 5.0, sp))
+        hip.check(L.tmh_smooth_f64_device(std, sstd, tmp, H, W, 5.0, sp))
+        hip.check(L.tmh_corrector_update_device(c, smean, sstd, sp))
+        hip.check(L.tmh_correct_u16_hist_device(c, h, d_in, d_out, N, -1, -1, sp))
         return _results(L, h, H, W, N)
 
     r1 = job()  # the production launch shapes (one Welford site part)
-    out1 = d_out.get(np.uint16, (N, npx))[::37].copy()
+    out1 = d_out.get((N, npx), np.uint16)[::37].copy()
     # the second job on the same handle (bench warm-up -> timed) with the
     # Welford launch split into 4 site parts (32 full-size sites each) + merge
     hip.check(L.tmh_stats_set_option(h, hip.TMH_OPT_WELFORD_PARTS, 4))
@@ -116,14 +113,12 @@ def test_headline_pipeline_fullsize(L):
         hip.check(L.tmh_stats_site_histogram(h, i, hip.ptr(sh)))
         site_hist[i] = sh
     order_stats = site_order_stats(L, h, (0, 63, N - 1), 100000)
-    sites = d_in.get(np.uint16, (N, H, W))
-    out = d_out.get(np.uint16, (N, H, W))
+    sites = d_in.get((N, H, W), np.uint16)
+    out = d_out.get((N, H, W), np.uint16)
     assert np.array_equal(out.reshape(N, npx)[::37], out1), "fused pass not repeatable"
-    gm, gs = smean.get(np.float64, (H, W)), sstd.get(np.float64, (H, W))
+    gm, gs = smean.get((H, W), np.float64), sstd.get((H, W), np.float64)
     L.tmh_corrector_destroy(c)
     L.tmh_stats_destroy(h)
-    for b in planes + [d_in, d_out]:
-        b.free()
 
     # the device generator is the bench's input: its host twin is bit-identical
     for i in (0, N - 1):
@@ -159,7 +154,7 @@ def test_headline_pipeline_fullsize(L):
 
 
 @pytest.mark.timeout(600)
-def test_bright_fullsize(L):
+def test_bright_fullsize(L, keep):
     """bright 16-bit data (lognormal(8.5, 0.6), about a third
     of the pixels >= 4,096) at full size.  The Welford pass takes its wide
     log10 path for most pixel groups and counts them; the automatic fused
@@ -173,7 +168,6 @@ def test_bright_fullsize(L):
     runs 100 bright sites through the bright pass and its 20,472-entry table.)"""
     import torch
 
-    from tmlibrary_amd import hip
     from tmlibrary_amd.image import ZERO_LOG10
     from tmlibrary_amd.synth import BRIGHT, synth_exact_host
     H, W, N = 2160, 2560, 64
@@ -182,48 +176,46 @@ def test_bright_fullsize(L):
     dev = torch.device("cuda", 0)
     stream = torch.cuda.Stream(dev)
     sp = C.c_void_p(stream.cuda_stream)
-    d_in, d_out = Dev(L, N * npx * 2), Dev(L, N * npx * 2)
-    planes = [Dev(L, npx * 8) for _ in range(5)]
+    d_in, d_out = keep(hip.DeviceBuffer(N * npx * 2)), keep(hip.DeviceBuffer(N * npx * 2))
+    planes = [keep(hip.DeviceBuffer(npx * 8)) for _ in range(5)]
     mean, std, smean, sstd, tmp = planes
-    hip.check(L.tmh_synth_sites_device(d_in.p, N, H, W, seed, channel, first, hip.TMH_SYNTH_BRIGHT, sp))
+    hip.check(L.tmh_synth_sites_device(d_in, N, H, W, seed, channel, first, hip.TMH_SYNTH_BRIGHT, sp))
     h = _stats_handle(L, H, W, hip.TMH_STATS_KEEP_SITE_HIST)
     hip.check(L.tmh_stats_set_stream(h, sp))
     c = C.c_void_p()
     L.tmh_synchronize(None)
-    hip.check(L.tmh_corrector_create_device(mean.p, std.p, H, W, 1, ZERO_LOG10, sp, C.byref(c)))
+    hip.check(L.tmh_corrector_create_device(mean, std, H, W, 1, ZERO_LOG10, sp, C.byref(c)))
     wide = []
 
     def job():
         hip.check(L.tmh_stats_reset(h))
-        hip.check(L.tmh_stats_update_welford_device(h, d_in.p, N, 1, sp))
+        hip.check(L.tmh_stats_update_welford_device(h, d_in, N, 1, sp))
         wg = C.c_uint64()
         hip.check(L.tmh_stats_wide_groups(h, C.byref(wg), None))
         wide.append(wg.value)
-        hip.check(L.tmh_stats_finalize_device(h, mean.p, std.p, sp))
-        hip.check(L.tmh_smooth_f64_device(mean.p, smean.p, tmp.p, H, W, 5.0, sp))
-        hip.check(L.tmh_smooth_f64_device(std.p, sstd.p, tmp.p, H, W, 5.0, sp))
-        hip.check(L.tmh_corrector_update_device(c, smean.p, sstd.p, sp))
-        hip.check(L.tmh_correct_u16_hist_device(c, h, d_in.p, d_out.p, N, -1, -1, sp))
+        hip.check(L.tmh_stats_finalize_device(h, mean, std, sp))
+        hip.check(L.tmh_smooth_f64_device(mean, smean, tmp, H, W, 5.0, sp))
+        hip.check(L.tmh_smooth_f64_device(std, sstd, tmp, H, W, 5.0, sp))
+        hip.check(L.tmh_corrector_update_device(c, smean, sstd, sp))
+        hip.check(L.tmh_correct_u16_hist_device(c, h, d_in, d_out, N, -1, -1, sp))
         return _results(L, h, H, W, N)
 
     r = job()  # automatic: wide
     pc, wb, fc = (C.c_uint32 * 3)(), C.c_int(), C.c_int()
     hip.check(L.tmh_stats_job_choice(h, pc, C.byref(wb), C.byref(fc)))
     assert wb.value == 1 and fc.value == 5, (list(pc), wb.value, fc.value)  # bright: both choices
-    out_auto = d_out.get(np.uint16, (N, npx))
+    out_auto = d_out.get((N, npx), np.uint16)
     hist0 = np.empty(65536, np.uint32)
     hip.check(L.tmh_stats_site_histogram(h, 0, hip.ptr(hist0)))
     hip.check(L.tmh_stats_set_option(h, hip.TMH_OPT_FUSED_CONFIG, 3))  # narrow, forced
     rn = job()
-    assert np.array_equal(d_out.get(np.uint16, (N, npx)), out_auto)
+    assert np.array_equal(d_out.get((N, npx), np.uint16), out_auto)
     assert np.array_equal(rn["acc"], r["acc"]) and np.array_equal(rn["hist"], r["hist"])
     assert np.array_equal(rn["mean"], r["mean"]) and np.array_equal(rn["std"], r["std"])
-    sites = d_in.get(np.uint16, (N, H, W))
-    gm, gs = smean.get(np.float64, (H, W)), sstd.get(np.float64, (H, W))
+    sites = d_in.get((N, H, W), np.uint16)
+    gm, gs = smean.get((H, W), np.float64), sstd.get((H, W), np.float64)
     L.tmh_corrector_destroy(c)
     L.tmh_stats_destroy(h)
-    for b in planes + [d_in, d_out]:
-        b.free()
 
     for i in (0, N - 1):
         assert np.array_equal(sites[i], synth_exact_host(H, W, seed, channel, first + i, BRIGHT))
@@ -267,13 +259,13 @@ def _wide_groups(sites):
 
 
 @pytest.mark.parametrize("cfg", [-1, 3, 5])
-def test_fused_multi_job_configs(L, cfg):
+def test_fused_multi_job_configs(L, keep, cfg):
     """cfg -1 is the automatic choice: job 1 is bright (lognormal(8.5, 0.6)),
     so the Welford count must select the wide configuration for it, and the
     synthetic jobs around it the narrow one."""
     import torch
 
-    from tmlibrary_amd import hip, synth
+    from tmlibrary_amd import synth
     from tmlibrary_amd.image import ZERO_LOG10
     H, W, n = 240, 320, 9
     npx = H * W
@@ -283,12 +275,12 @@ def test_fused_multi_job_configs(L, cfg):
     h = _stats_handle(L, H, W, hip.TMH_STATS_KEEP_SITE_HIST)
     hip.check(L.tmh_stats_set_option(h, hip.TMH_OPT_FUSED_CONFIG, cfg))
     hip.check(L.tmh_stats_set_stream(h, sp1))
-    d_in, d_out = Dev(L, n * npx * 2), Dev(L, n * npx * 2)
-    planes = [Dev(L, npx * 8) for _ in range(5)]
+    d_in, d_out = keep(hip.DeviceBuffer(n * npx * 2)), keep(hip.DeviceBuffer(n * npx * 2))
+    planes = [keep(hip.DeviceBuffer(npx * 8)) for _ in range(5)]
     mean, std, smean, sstd, tmp = planes
     c = C.c_void_p()  # its stream is stream 2; coefficients come from each job below
     L.tmh_synchronize(None)
-    hip.check(L.tmh_corrector_create_device(mean.p, std.p, H, W, 1, ZERO_LOG10, sp2, C.byref(c)))
+    hip.check(L.tmh_corrector_create_device(mean, std, H, W, 1, ZERO_LOG10, sp2, C.byref(c)))
     L.tmh_synchronize(None)
     for k in range(3):
         bright = cfg == -1 and k == 1
@@ -298,11 +290,11 @@ def test_fused_multi_job_configs(L, cfg):
         # fused pass on stream 2 (tmh_correct_u16_hist_device orders itself
         # after stream 1 and makes stream 1 wait for it)
         hip.check(L.tmh_stats_reset(h))
-        hip.check(L.tmh_stats_update_welford_device(h, d_in.p, n, 1, None))
-        hip.check(L.tmh_stats_finalize_device(h, mean.p, std.p, None))
-        hip.check(L.tmh_smooth_f64_device(mean.p, smean.p, tmp.p, H, W, 5.0, sp1))
-        hip.check(L.tmh_smooth_f64_device(std.p, sstd.p, tmp.p, H, W, 5.0, sp1))
-        hip.check(L.tmh_corrector_update_device(c, smean.p, sstd.p, sp1))
+        hip.check(L.tmh_stats_update_welford_device(h, d_in, n, 1, None))
+        hip.check(L.tmh_stats_finalize_device(h, mean, std, None))
+        hip.check(L.tmh_smooth_f64_device(mean, smean, tmp, H, W, 5.0, sp1))
+        hip.check(L.tmh_smooth_f64_device(std, sstd, tmp, H, W, 5.0, sp1))
+        hip.check(L.tmh_corrector_update_device(c, smean, sstd, sp1))
         wg, ws = C.c_uint64(), C.c_int64()
         hip.check(L.tmh_stats_wide_groups(h, C.byref(wg), C.byref(ws)))
         groups = n * npx // 8
@@ -315,7 +307,7 @@ def test_fused_multi_job_configs(L, cfg):
         hip.check(L.tmh_stats_job_choice(h, pc, C.byref(wb), C.byref(fc)))
         assert pc[0] == 16384 and wb.value == int(bright), (cfg, k, list(pc), wb.value)
         assert fc.value == (cfg if cfg >= 0 else (5 if bright else 3)), (cfg, k, fc.value)
-        hip.check(L.tmh_correct_u16_hist_device(c, h, d_in.p, d_out.p, n, -1, -1, None))
+        hip.check(L.tmh_correct_u16_hist_device(c, h, d_in, d_out, n, -1, -1, None))
         r = _results(L, h, H, W, n)  # on stream 1: waits for stream 2's fused pass
         hip.check(L.tmh_stats_wide_groups(h, C.byref(wg), C.byref(ws)))
         assert wg.value == 0 and ws.value == 0  # consumed by the fused pass
@@ -328,15 +320,13 @@ def test_fused_multi_job_configs(L, cfg):
             sh = np.empty(65536, np.uint32)
             hip.check(L.tmh_stats_site_histogram(h, i, hip.ptr(sh)))
             assert np.array_equal(sh.astype(np.uint64), orc.histogram_u16(sites[i])), (cfg, k, i)
-        out = d_out.get(np.uint16, sites.shape)
+        out = d_out.get(sites.shape, np.uint16)
         sm_ref, ss_ref = orc.smooth_reflect(ref.mean, 5), orc.smooth_reflect(ref.std, 5)
         for i in (0, n - 1):
             worst, flips, _ = dn_report(out[i], orc.correct_illumination(sites[i], sm_ref, ss_ref))
             assert worst <= 1 and flips == 0, (cfg, k, i, worst, flips)
     L.tmh_corrector_destroy(c)
     L.tmh_stats_destroy(h)
-    for b in planes + [d_in, d_out]:
-        b.free()
 
 
 def _groups_ge(sites, v):
@@ -346,7 +336,7 @@ def _groups_ge(sites, v):
 
 
 @pytest.mark.parametrize("cfg", [-1, 3, 5])
-def test_very_wide_jobs(L, cfg):
+def test_very_wide_jobs(L, keep, cfg):
     """Very wide sites (a third or more of the 8-pixel groups hold a value
     >= 16,384): with the automatic configuration the fused pass runs without
     its histogram and k_hist_site_u16 builds the exact per-site histograms in
@@ -360,7 +350,7 @@ def test_very_wide_jobs(L, cfg):
     values within 1 DN of the oracle (stats.py:64-121, image.py:599-631)."""
     import torch
 
-    from tmlibrary_amd import hip, synth
+    from tmlibrary_amd import synth
     from tmlibrary_amd.image import ZERO_LOG10
     H, W, n = 288, 320, 6  # 92,160 pixels per site: room for a 70,000-pixel value
     npx = H * W
@@ -370,12 +360,12 @@ def test_very_wide_jobs(L, cfg):
     h = _stats_handle(L, H, W, hip.TMH_STATS_KEEP_SITE_HIST)
     hip.check(L.tmh_stats_set_option(h, hip.TMH_OPT_FUSED_CONFIG, cfg))
     hip.check(L.tmh_stats_set_stream(h, sp))
-    d_in, d_out = Dev(L, n * npx * 2), Dev(L, n * npx * 2)
-    planes = [Dev(L, npx * 8) for _ in range(5)]
+    d_in, d_out = keep(hip.DeviceBuffer(n * npx * 2)), keep(hip.DeviceBuffer(n * npx * 2))
+    planes = [keep(hip.DeviceBuffer(npx * 8)) for _ in range(5)]
     mean, std, smean, sstd, tmp = planes
     c = C.c_void_p()
     L.tmh_synchronize(None)
-    hip.check(L.tmh_corrector_create_device(mean.p, std.p, H, W, 1, ZERO_LOG10, sp, C.byref(c)))
+    hip.check(L.tmh_corrector_create_device(mean, std, H, W, 1, ZERO_LOG10, sp, C.byref(c)))
     L.tmh_synchronize(None)
     for k in range(2):
         sites = np.stack([synth.synth_exact_host(H, W, 91 + k, 1, i, synth.UNIFORM)
@@ -390,13 +380,13 @@ def test_very_wide_jobs(L, cfg):
             sites[5].reshape(-1)[:50000] = 12345
         d_in.put(sites)
         hip.check(L.tmh_stats_reset(h))
-        hip.check(L.tmh_stats_update_welford_device(h, d_in.p, n, 1, sp))
-        hip.check(L.tmh_stats_finalize_device(h, mean.p, std.p, sp))
-        hip.check(L.tmh_smooth_f64_device(mean.p, smean.p, tmp.p, H, W, 5.0, sp))
-        hip.check(L.tmh_smooth_f64_device(std.p, sstd.p, tmp.p, H, W, 5.0, sp))
-        hip.check(L.tmh_corrector_update_device(c, smean.p, sstd.p, sp))
+        hip.check(L.tmh_stats_update_welford_device(h, d_in, n, 1, sp))
+        hip.check(L.tmh_stats_finalize_device(h, mean, std, sp))
+        hip.check(L.tmh_smooth_f64_device(mean, smean, tmp, H, W, 5.0, sp))
+        hip.check(L.tmh_smooth_f64_device(std, sstd, tmp, H, W, 5.0, sp))
+        hip.check(L.tmh_corrector_update_device(c, smean, sstd, sp))
         assert _groups_ge(sites, 16384) >= 0.33 * n * npx // 8  # very wide
-        hip.check(L.tmh_correct_u16_hist_device(c, h, d_in.p, d_out.p, n, -1, -1, sp))
+        hip.check(L.tmh_correct_u16_hist_device(c, h, d_in, d_out, n, -1, -1, sp))
         r = _results(L, h, H, W, n)
         ref = orc.run_illumstats(list(sites))
         assert r["n"] == n
@@ -409,7 +399,7 @@ def test_very_wide_jobs(L, cfg):
             hip.check(L.tmh_stats_site_histogram(h, i, hip.ptr(sh)))
             assert np.array_equal(sh.astype(np.uint64), orc.histogram_u16(sites[i])), (cfg, k, i)
         check_order_stats([sites[i] for i in (0, 2)], site_order_stats(L, h, (0, 2), 100000))
-        out = d_out.get(np.uint16, sites.shape)
+        out = d_out.get(sites.shape, np.uint16)
         sm_ref, ss_ref = orc.smooth_reflect(ref.mean, 5), orc.smooth_reflect(ref.std, 5)
         for i in (0, 2, n - 1):
             worst, flips, _ = dn_report(out[i], orc.correct_illumination(sites[i], sm_ref, ss_ref))
@@ -418,20 +408,18 @@ def test_very_wide_jobs(L, cfg):
     sites = np.stack([synth.synth_exact_host(H, W, 99, 1, i, synth.STANDARD) for i in range(n)])
     d_in.put(sites)
     hip.check(L.tmh_stats_reset(h))
-    hip.check(L.tmh_stats_update_welford_device(h, d_in.p, n, 1, sp))
-    hip.check(L.tmh_stats_finalize_device(h, mean.p, std.p, sp))
-    hip.check(L.tmh_corrector_update_device(c, mean.p, std.p, sp))
-    hip.check(L.tmh_correct_u16_hist_device(c, h, d_in.p, d_out.p, n, -1, -1, sp))
+    hip.check(L.tmh_stats_update_welford_device(h, d_in, n, 1, sp))
+    hip.check(L.tmh_stats_finalize_device(h, mean, std, sp))
+    hip.check(L.tmh_corrector_update_device(c, mean, std, sp))
+    hip.check(L.tmh_correct_u16_hist_device(c, h, d_in, d_out, n, -1, -1, sp))
     r = _results(L, h, H, W, n)
     assert np.array_equal(r["hist"], sum(orc.histogram_u16(s) for s in sites))
     assert np.array_equal(r["acc"], orc.run_illumstats(list(sites)).percentile_sums)
     L.tmh_corrector_destroy(c)
     L.tmh_stats_destroy(h)
-    for b in planes + [d_in, d_out]:
-        b.free()
 
 
-def test_packed_counters_wrap(L):
+def test_packed_counters_wrap(L, keep):
     """Fused configuration 5 (four sites per unit, u16 LDS counters packed two
     sites to a word, 8 bands): at 768 x 768 a band holds 73,728 pixels of a
     site, so a value filling a band wraps its 16-bit counter.  The flush's
@@ -440,7 +428,7 @@ def test_packed_counters_wrap(L):
     bright site, a bright site, and a site with a value >= 16,384 in every
     pixel group.  Per-site histograms, percentile sums bit-exact; mean/std
     1e-6 (stats.py:64-121)."""
-    from tmlibrary_amd import hip, synth
+    from tmlibrary_amd import synth
     H, W, n = 768, 768, 5
     npx = H * W
     sites = np.stack([synth.synth_exact_host(H, W, 5 + i, 0, i, synth.BRIGHT) for i in range(n)])
@@ -450,21 +438,21 @@ def test_packed_counters_wrap(L):
     sites[4, :, ::8] = 40000
     h = _stats_handle(L, H, W, hip.TMH_STATS_KEEP_SITE_HIST)
     hip.check(L.tmh_stats_set_option(h, hip.TMH_OPT_FUSED_CONFIG, 5))
-    d_in, d_out = Dev(L, n * npx * 2), Dev(L, n * npx * 2)
-    planes = [Dev(L, npx * 8) for _ in range(5)]
+    d_in, d_out = keep(hip.DeviceBuffer(n * npx * 2)), keep(hip.DeviceBuffer(n * npx * 2))
+    planes = [keep(hip.DeviceBuffer(npx * 8)) for _ in range(5)]
     mean, std, smean, sstd, tmp = planes
     from tmlibrary_amd.image import ZERO_LOG10
     c = C.c_void_p()
     L.tmh_synchronize(None)
-    hip.check(L.tmh_corrector_create_device(mean.p, std.p, H, W, 1, ZERO_LOG10, None, C.byref(c)))
+    hip.check(L.tmh_corrector_create_device(mean, std, H, W, 1, ZERO_LOG10, None, C.byref(c)))
     d_in.put(sites)
     hip.check(L.tmh_stats_reset(h))
-    hip.check(L.tmh_stats_update_welford_device(h, d_in.p, n, 1, None))
-    hip.check(L.tmh_stats_finalize_device(h, mean.p, std.p, None))
-    hip.check(L.tmh_smooth_f64_device(mean.p, smean.p, tmp.p, H, W, 5.0, None))
-    hip.check(L.tmh_smooth_f64_device(std.p, sstd.p, tmp.p, H, W, 5.0, None))
-    hip.check(L.tmh_corrector_update_device(c, smean.p, sstd.p, None))
-    hip.check(L.tmh_correct_u16_hist_device(c, h, d_in.p, d_out.p, n, -1, -1, None))
+    hip.check(L.tmh_stats_update_welford_device(h, d_in, n, 1, None))
+    hip.check(L.tmh_stats_finalize_device(h, mean, std, None))
+    hip.check(L.tmh_smooth_f64_device(mean, smean, tmp, H, W, 5.0, None))
+    hip.check(L.tmh_smooth_f64_device(std, sstd, tmp, H, W, 5.0, None))
+    hip.check(L.tmh_corrector_update_device(c, smean, sstd, None))
+    hip.check(L.tmh_correct_u16_hist_device(c, h, d_in, d_out, n, -1, -1, None))
     r = _results(L, h, H, W, n)
     ref = orc.run_illumstats(list(sites))
     assert r["n"] == n
@@ -477,5 +465,3 @@ def test_packed_counters_wrap(L):
     assert np.array_equal(r["acc"], ref.percentile_sums)
     L.tmh_corrector_destroy(c)
     L.tmh_stats_destroy(h)
-    for b in planes + [d_in, d_out]:
-        b.free()

@@ -19,7 +19,6 @@ at every workgroup width; tests/test_inflate_host.py runs the same cases
 through the host build of the core under the sanitizers.  tmh_place_chunks_device
 is checked alone against numpy slice assignment.
 """
-import ctypes as C
 import os
 import zlib
 
@@ -27,13 +26,14 @@ import numpy as np
 import pytest
 
 import inflate_cases as ic
+from tmlibrary_amd import hip
+from util import keep  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def L():
-    from tmlibrary_amd import hip
     return hip.lib()
 
 
@@ -73,8 +73,6 @@ def _streams():
 
 def _run(L, streams, raw_lens=None):
     """tmh_inflate_device over the streams as one launch; returns (outputs, statuses)."""
-    from tmlibrary_amd import hip
-    from test_gpu_parity import Dev
     n = len(streams)
     blob = b"".join(s for _, _, s in streams)
     tab = np.zeros(n, hip.ZCHUNK_DTYPE)
@@ -84,21 +82,19 @@ def _run(L, streams, raw_lens=None):
         tab[i] = (off, len(s), roff, rl, i, 0, 0, 0, 0)
         off += len(s)
         roff += rl
-    d_src, d_tab = Dev(L, max(len(blob), 1)), Dev(L, tab.nbytes)
-    d_raw, d_st = Dev(L, max(roff, 1)), Dev(L, 4 * n)
     raw_max = int(tab["raw_len"].max())
     scr = int(L.tmh_inflate_scratch_bytes(n, raw_max))
-    d_scr = Dev(L, scr)
-    d_src.put(np.frombuffer(blob, np.uint8))
-    d_tab.put(tab)
-    hip.check(L.tmh_inflate_device(d_src.p, len(blob), d_tab.p, n, raw_max, d_raw.p, roff,
-                                   d_scr.p, scr, d_st.p, None))
-    assert L.tmh_synchronize(None) == 0
-    rawout = d_raw.get(np.uint8, (max(roff, 1),))
-    st = d_st.get(np.int32, (n,))
+    with hip.DeviceBuffer(max(len(blob), 1)) as d_src, hip.DeviceBuffer(tab.nbytes) as d_tab, \
+            hip.DeviceBuffer(max(roff, 1)) as d_raw, hip.DeviceBuffer(4 * n) as d_st, \
+            hip.DeviceBuffer(max(scr, 1)) as d_scr:
+        d_src.put(np.frombuffer(blob, np.uint8))
+        d_tab.put(tab)
+        hip.check(L.tmh_inflate_device(d_src, len(blob), d_tab, n, raw_max, d_raw, roff,
+                                       d_scr, scr, d_st, None))
+        assert L.tmh_synchronize(None) == 0
+        rawout = d_raw.get((max(roff, 1),), np.uint8)
+        st = d_st.get((n,), np.int32)
     outs = [rawout[t["raw_off"]:t["raw_off"] + t["raw_len"]].tobytes() for t in tab]
-    for b in (d_src, d_tab, d_raw, d_st, d_scr):
-        b.free()
     return outs, st
 
 
@@ -131,7 +127,6 @@ def test_inflate_many_streams_one_launch(L):
 def test_inflate_corrupt_streams_reported(L):
     """Corrupt chunks get their own status; the good chunks of the same
     launch still decode exactly."""
-    from tmlibrary_amd import hip
     raw = (np.arange(20000, dtype=np.uint16) % 1234).tobytes()
     good = zlib.compress(raw, 6)
     flipped = bytearray(good)
@@ -254,17 +249,15 @@ class _Device:
         self.L, self.bufs = L, {}
 
     def buf(self, key, nbytes):
-        from test_gpu_parity import Dev
         b = self.bufs.get(key)
         if b is None or b.nbytes < nbytes:
             if b is not None:
                 b.free()
-            b = self.bufs[key] = Dev(self.L, max(nbytes, 1) * 2)
+            b = self.bufs[key] = hip.DeviceBuffer(max(nbytes, 1) * 2)
         return b
 
     def run(self, blob, rows, raw_bytes):
         """The whole raw buffer (pre-filled with the sentinel) and the statuses."""
-        from tmlibrary_amd import hip
         from test_inflate_host import table_of
         L, n = self.L, len(rows)
         tab = table_of(rows)
@@ -277,10 +270,10 @@ class _Device:
         d_tab.put(tab)
         d_raw.put(np.full(max(raw_bytes, 1), ic.SENTINEL, np.uint8))
         d_st.put(np.full(n, 0x7F7F7F7F, np.int32))
-        hip.check(L.tmh_inflate_device(d_src.p, len(blob), d_tab.p, n, raw_max, d_raw.p, raw_bytes,
-                                       d_scr.p, scr, d_st.p, None))
+        hip.check(L.tmh_inflate_device(d_src, len(blob), d_tab, n, raw_max, d_raw, raw_bytes,
+                                       d_scr, scr, d_st, None))
         assert L.tmh_synchronize(None) == 0
-        return d_raw.get(np.uint8, (max(raw_bytes, 1),))[:raw_bytes], d_st.get(np.int32, (n,))
+        return d_raw.get((max(raw_bytes, 1),), np.uint8)[:raw_bytes], d_st.get((n,), np.int32)
 
     def free(self):
         for b in self.bufs.values():
@@ -364,12 +357,10 @@ def test_invalid_streams_device_equals_host_core(dev, host_exe, tmp_path):
     (17, 20, np.uint32, 8, 8, 0),
     (16, 32, np.uint16, 16, 32, 0),   # one chunk per image
 ])
-def test_place_chunks_against_slice_assignment(L, H, W, dtype, cr, cc, shift):
+def test_place_chunks_against_slice_assignment(L, keep, H, W, dtype, cr, cc, shift):
     """tmh_place_chunks_device on a raw buffer of known bytes equals numpy
     slice assignment; a chunk left out of the table leaves its pixels alone,
     and so does the border around the images."""
-    from tmlibrary_amd import hip
-    from test_gpu_parity import Dev
     rng = np.random.default_rng(H * W + shift)
     es, n_img, border = np.dtype(dtype).itemsize, 3, 64
     grid = [(i, r, c) for i in range(n_img) for r in range(0, H, cr) for c in range(0, W, cc)]
@@ -389,16 +380,15 @@ def test_place_chunks_against_slice_assignment(L, H, W, dtype, cr, cc, shift):
             rows, cols = min(cr, H - r), min(cc, W - c)
             want[i, r:r + rows, c * es:(c + cols) * es] = chunks[g].reshape(cr, cc * es)[:rows, :cols * es]
     tab = np.delete(tab, skipped) if skipped >= 0 else tab
-    d_raw, d_tab, d_img = Dev(L, raw.nbytes), Dev(L, tab.nbytes), Dev(L, want.size + 2 * border)
+    d_raw, d_tab = keep(hip.DeviceBuffer(raw.nbytes)), keep(hip.DeviceBuffer(tab.nbytes))
+    d_img = keep(hip.DeviceBuffer(want.size + 2 * border))
     d_raw.put(raw)
     d_tab.put(tab)
     d_img.put(np.full(want.size + 2 * border, ic.SENTINEL, np.uint8))
-    hip.check(L.tmh_place_chunks_device(d_raw.p, d_tab.p, len(tab), H, W, es, cr, cc,
-                                        C.c_void_p(d_img.p.value + border), None))
+    hip.check(L.tmh_place_chunks_device(d_raw, d_tab, len(tab), H, W, es, cr, cc,
+                                        d_img.at(border), None))
     assert L.tmh_synchronize(None) == 0
-    got = d_img.get(np.uint8, (want.size + 2 * border,))
-    for b in (d_raw, d_tab, d_img):
-        b.free()
+    got = d_img.get((want.size + 2 * border,), np.uint8)
     assert np.all(got[:border] == ic.SENTINEL) and np.all(got[-border:] == ic.SENTINEL)
     assert np.array_equal(got[border:-border].reshape(want.shape), want)
     if skipped >= 0:

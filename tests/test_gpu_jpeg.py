@@ -4,6 +4,7 @@ Python layer (``Pyramid.encode_level`` / ``iter_jpeg_tiles``,
 libjpeg-turbo wrote (tests/golden/jpeg_tiles.npz; no test here imports
 Pillow) and against tests/jpeg_literal.py, which the CPU suite pins to them.
 """
+import contextlib
 import ctypes as C
 import hashlib
 import os
@@ -13,6 +14,7 @@ import pytest
 
 import jpeg_literal as jl
 import pyramid_literal as lit
+from tmlibrary_amd import hip
 from util import REPO
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +24,6 @@ GUARD = 64
 
 @pytest.fixture(scope="module")
 def L():
-    from tmlibrary_amd import hip
     return hip.lib()
 
 
@@ -44,27 +45,6 @@ def literal():
     return get
 
 
-class Dev(object):
-    """A device buffer holding a copy of ``a``."""
-
-    def __init__(self, L, a):
-        from tmlibrary_amd import hip
-        self.L, self.hip = L, hip
-        a = np.ascontiguousarray(a)
-        self.nbytes, self.dtype = a.nbytes, a.dtype
-        self.p = C.c_void_p()
-        hip.check(L.tmh_malloc_device(C.byref(self.p), a.nbytes))
-        hip.check(L.tmh_memcpy(self.p, hip.ptr(a), a.nbytes, 0, None))
-
-    def get(self):
-        out = np.empty(self.nbytes // self.dtype.itemsize, dtype=self.dtype)
-        self.hip.check(self.L.tmh_memcpy(self.hip.ptr(out), self.p, out.nbytes, 1, None))
-        return out
-
-    def free(self):
-        self.L.tmh_free_device(self.p)
-
-
 def _level(tiles, rows, cols, surround=0):
     """[rows][cols][256][256] storage with tile t's array in its corner and
     ``surround`` in the rest of a ragged tile's storage."""
@@ -77,31 +57,27 @@ def _level(tiles, rows, cols, surround=0):
 def _encode(L, level, rows, cols, last_h, last_w, quality, write=True):
     """One writing (or measuring) call -> (rc, blob incl. guard, offsets, total)."""
     n = rows * cols
-    d_level = Dev(L, level)
-    d_off = Dev(L, np.full(n + 1, -1, dtype=np.int64))
     total = C.c_int64(-1)
-    d_out = None
-    try:
-        rc = L.tmh_jpeg_encode_level_device(d_level.p, rows, cols, last_h, last_w, quality, None, 0,
-                                            d_off.p, C.byref(total), None)
+    with contextlib.ExitStack() as stack:
+        d_level = stack.enter_context(hip.DeviceBuffer.from_array(level))
+        d_off = stack.enter_context(hip.DeviceBuffer.from_array(np.full(n + 1, -1, dtype=np.int64)))
+        rc = L.tmh_jpeg_encode_level_device(d_level, rows, cols, last_h, last_w, quality, None, 0,
+                                            d_off, C.byref(total), None)
         assert rc == 0, L.tmh_last_error()
-        measured = d_off.get()
+        measured = d_off.get(n + 1, np.int64)
         assert total.value == measured[n] and measured[0] == 0
         if not write:
             return rc, None, measured, total.value
-        d_out = Dev(L, np.full(total.value + GUARD, 0x5C, dtype=np.uint8))
+        d_out = stack.enter_context(hip.DeviceBuffer.from_array(
+            np.full(total.value + GUARD, 0x5C, dtype=np.uint8)))
         total2 = C.c_int64(-1)
-        rc = L.tmh_jpeg_encode_level_device(d_level.p, rows, cols, last_h, last_w, quality, d_out.p,
-                                            total.value, d_off.p, C.byref(total2), None)
+        rc = L.tmh_jpeg_encode_level_device(d_level, rows, cols, last_h, last_w, quality, d_out,
+                                            total.value, d_off, C.byref(total2), None)
         assert rc == 0, L.tmh_last_error()
-        offsets = d_off.get()
+        offsets = d_off.get(n + 1, np.int64)
         # the measuring call and the writing call agree
         assert total2.value == total.value and np.array_equal(offsets, measured)
-        return rc, d_out.get(), offsets, total.value
-    finally:
-        for d in (d_level, d_off, d_out):
-            if d is not None:
-                d.free()
+        return rc, d_out.get(total.value + GUARD, np.uint8), offsets, total.value
 
 
 def _files(blob, offsets):
@@ -152,40 +128,34 @@ def test_mixed_ragged_level(L, literal):
 # ---- measure and capacity --------------------------------------------------------------------
 
 def test_capacity_one_short_writes_nothing(L):
-    from tmlibrary_amd import hip
     tiles = [jl.case_array(k) for k in ("cells", "zeros", "stripes")]
     _, _, measured, total = _encode(L, _level(tiles, 1, 3), 1, 3, T, T, 95, write=False)
     assert np.all(np.diff(measured) > 0)
-    d_level = Dev(L, _level(tiles, 1, 3))
-    d_off = Dev(L, np.full(4, -1, dtype=np.int64))
-    d_out = Dev(L, np.full(total + GUARD, 0x5C, dtype=np.uint8))
-    try:
+    with hip.DeviceBuffer.from_array(_level(tiles, 1, 3)) as d_level, \
+            hip.DeviceBuffer.from_array(np.full(4, -1, dtype=np.int64)) as d_off, \
+            hip.DeviceBuffer.from_array(np.full(total + GUARD, 0x5C, dtype=np.uint8)) as d_out:
         got = C.c_int64(-1)
-        rc = L.tmh_jpeg_encode_level_device(d_level.p, 1, 3, T, T, 95, d_out.p, total - 1, d_off.p,
+        rc = L.tmh_jpeg_encode_level_device(d_level, 1, 3, T, T, 95, d_out, total - 1, d_off,
                                             C.byref(got), None)
         assert rc == hip.TMH_EINVAL and len(L.tmh_last_error()) > 0
-        assert got.value == total and np.array_equal(d_off.get(), measured)
-        assert np.all(d_out.get() == 0x5C), "a refused call wrote output"
-        rc = L.tmh_jpeg_encode_level_device(d_level.p, 1, 3, T, T, 95, d_out.p, total, d_off.p,
+        assert got.value == total and np.array_equal(d_off.get(4, np.int64), measured)
+        assert np.all(d_out.get(total + GUARD, np.uint8) == 0x5C), "a refused call wrote output"
+        rc = L.tmh_jpeg_encode_level_device(d_level, 1, 3, T, T, 95, d_out, total, d_off,
                                             C.byref(got), None)
         assert rc == 0 and got.value == total
-        blob = d_out.get()
+        blob = d_out.get(total + GUARD, np.uint8)
         assert np.all(blob[total:] == 0x5C) and blob[total - 2:total].tolist() == [0xFF, 0xD9]
-    finally:
-        for d in (d_level, d_off, d_out):
-            d.free()
 
 
 # ---- bad arguments ------------------------------------------------------------------------------
 
 def test_bad_arguments_launch_nothing(L):
-    from tmlibrary_amd import hip
-    d_level = Dev(L, _level([jl.case_array("cells")] * 2, 1, 2))
-    d_off = Dev(L, np.full(3, -7, dtype=np.int64))
-    d_out = Dev(L, np.full(4096, 0x5C, dtype=np.uint8))
+    d_level = hip.DeviceBuffer.from_array(_level([jl.case_array("cells")] * 2, 1, 2))
+    d_off = hip.DeviceBuffer.from_array(np.full(3, -7, dtype=np.int64))
+    d_out = hip.DeviceBuffer.from_array(np.full(4096, 0x5C, dtype=np.uint8))
     total = C.c_int64(-7)
 
-    def call(level=d_level.p, r=1, c=2, h=T, w=T, out=d_out.p, cap=4096, off=d_off.p,
+    def call(level=d_level, r=1, c=2, h=T, w=T, out=d_out, cap=4096, off=d_off,
              tot=C.byref(total)):
         return L.tmh_jpeg_encode_level_device(level, r, c, h, w, 95, out, cap, off, tot, None)
 
@@ -206,17 +176,14 @@ def test_bad_arguments_launch_nothing(L):
         "host form last width 300": lambda: L.tmh_jpeg_encode_level(
             hip.ptr(host), 1, 1, T, 300, 95, None, 0, hip.ptr(hoff), C.byref(total)),
     }
-    try:
+    with d_level, d_off, d_out:
         for name, f in bad.items():
             assert f() == hip.TMH_EINVAL, name
             assert len(L.tmh_last_error()) > 0, name
         hip.check(L.tmh_synchronize(None))
         assert total.value == -7 and np.all(hoff == -7)
-        assert np.all(d_off.get() == -7), "a refused call wrote offsets"
-        assert np.all(d_out.get() == 0x5C), "a refused call wrote output"
-    finally:
-        for d in (d_level, d_off, d_out):
-            d.free()
+        assert np.all(d_off.get(3, np.int64) == -7), "a refused call wrote offsets"
+        assert np.all(d_out.get(4096, np.uint8) == 0x5C), "a refused call wrote output"
 
 
 # ---- quality clamp --------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ the CPU suite pins to it.  The files that must be refused are the ones
 tests/test_jpeg_decode_cpu.py has already run through the same decoder code
 on the CPU, under sanitizers.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -16,6 +17,7 @@ import pytest
 import jpeg_decode_literal as jd
 import jpeg_literal as jl
 import pyramid_literal as lit
+from tmlibrary_amd import hip
 from util import REPO
 
 pytestmark = pytest.mark.gpu
@@ -25,34 +27,12 @@ GOLDEN = os.path.join(REPO, "tests", "golden", "jpeg_decoded.npz")
 
 @pytest.fixture(scope="module")
 def L():
-    from tmlibrary_amd import hip
     return hip.lib()
 
 
 @pytest.fixture(scope="module")
 def goldens():
     return jd.load_goldens(GOLDEN)
-
-
-class Dev(object):
-    """A device buffer holding a copy of ``a``."""
-
-    def __init__(self, L, a):
-        from tmlibrary_amd import hip
-        self.L, self.hip = L, hip
-        a = np.ascontiguousarray(a)
-        self.nbytes, self.dtype = a.nbytes, a.dtype
-        self.p = C.c_void_p()
-        hip.check(L.tmh_malloc_device(C.byref(self.p), max(a.nbytes, 16)))
-        hip.check(L.tmh_memcpy(self.p, hip.ptr(a), a.nbytes, 0, None))
-
-    def get(self):
-        out = np.empty(self.nbytes // self.dtype.itemsize, dtype=self.dtype)
-        self.hip.check(self.L.tmh_memcpy(self.hip.ptr(out), self.p, out.nbytes, 1, None))
-        return out
-
-    def free(self):
-        self.L.tmh_free_device(self.p)
 
 
 def _level(tiles, surround=0):
@@ -63,17 +43,13 @@ def _level(tiles, surround=0):
 
 
 def _roundtrip_device(L, level, rows, cols, last_h, last_w, quality):
-    from tmlibrary_amd import hip
-    d_in, d_out = Dev(L, level), Dev(L, np.full(level.shape, 0x5C, dtype=np.uint8))
-    try:
-        hip.check(L.tmh_jpeg_roundtrip_level_device(d_in.p, rows, cols, last_h, last_w, quality,
-                                                    d_out.p, None))
+    with hip.DeviceBuffer.from_array(level) as d_in, \
+            hip.DeviceBuffer.from_array(np.full(level.shape, 0x5C, dtype=np.uint8)) as d_out:
+        hip.check(L.tmh_jpeg_roundtrip_level_device(d_in, rows, cols, last_h, last_w, quality,
+                                                    d_out, None))
         hip.check(L.tmh_synchronize(None))
-        assert np.array_equal(d_in.get().reshape(level.shape), level), "the input was written"
-        return d_out.get().reshape(level.shape)
-    finally:
-        d_in.free()
-        d_out.free()
+        assert np.array_equal(d_in.get(level.shape, np.uint8), level), "the input was written"
+        return d_out.get(level.shape, np.uint8)
 
 
 def _mixed_level():
@@ -96,7 +72,6 @@ def mixed():
 # ---- the round trip of a level -----------------------------------------------------------
 
 def test_roundtrip_every_golden_as_a_one_tile_level(L, goldens):
-    from tmlibrary_amd import hip
     for name, a, q, _, want in goldens:
         h, w = a.shape
         level = _level([a], surround=0xAA)
@@ -126,11 +101,10 @@ def test_roundtrip_one_by_one_level(L):
 
 
 def test_roundtrip_bad_arguments_launch_nothing(L):
-    from tmlibrary_amd import hip
-    d_in = Dev(L, _level([jl.case_array("cells")] * 2))
-    d_out = Dev(L, np.full((2, T, T), 0x5C, dtype=np.uint8))
+    d_in = hip.DeviceBuffer.from_array(_level([jl.case_array("cells")] * 2))
+    d_out = hip.DeviceBuffer.from_array(np.full((2, T, T), 0x5C, dtype=np.uint8))
 
-    def call(level=d_in.p, r=1, c=2, h=T, w=T, out=d_out.p):
+    def call(level=d_in, r=1, c=2, h=T, w=T, out=d_out):
         return L.tmh_jpeg_roundtrip_level_device(level, r, c, h, w, 95, out, None)
 
     host = np.zeros((T, T), dtype=np.uint8)
@@ -138,7 +112,7 @@ def test_roundtrip_bad_arguments_launch_nothing(L):
     bad = {
         "NULL level": lambda: call(level=None),
         "NULL output": lambda: call(out=None),
-        "in place": lambda: call(out=d_in.p),
+        "in place": lambda: call(out=d_in),
         "rows 0": lambda: call(r=0),
         "cols negative": lambda: call(c=-1),
         "last height 0": lambda: call(h=0),
@@ -149,41 +123,38 @@ def test_roundtrip_bad_arguments_launch_nothing(L):
         "host form last width 300": lambda: L.tmh_jpeg_roundtrip_level(
             hip.ptr(host), 1, 1, T, 300, 95, hip.ptr(hout)),
     }
-    try:
+    with d_in, d_out:
         for name, f in bad.items():
             assert f() == hip.TMH_EINVAL, name
             assert len(L.tmh_last_error()) > 0, name
         hip.check(L.tmh_synchronize(None))
-        assert np.all(d_out.get() == 0x5C) and np.all(hout == 0x5C), "a refused call wrote output"
-    finally:
-        d_in.free()
-        d_out.free()
+        assert np.all(d_out.get((2, T, T), np.uint8) == 0x5C) and np.all(hout == 0x5C), \
+            "a refused call wrote output"
 
 
 # ---- the decoder of files -----------------------------------------------------------------
 
 def _decode_device(L, files):
     """One call of the device entry -> (tiles [n][256][256], dims, status)."""
-    from tmlibrary_amd import hip
     n = len(files)
     offsets = np.concatenate([[0], np.cumsum([len(f) for f in files])]).astype(np.int64)
     blob = np.frombuffer(b"".join(files), np.uint8)
-    d_blob, d_off = Dev(L, blob), Dev(L, offsets)
-    d_tiles = Dev(L, np.full((n + 1, T, T), 0x5C, dtype=np.uint8))      # one tile of guard
-    d_dims, d_status = Dev(L, np.full((n, 2), -7, np.int32)), Dev(L, np.full(n, -7, np.int32))
-    try:
-        hip.check(L.tmh_jpeg_decode_tiles_device(d_blob.p, d_off.p, n, d_tiles.p, d_dims.p,
-                                                 d_status.p, None))
-        tiles = d_tiles.get().reshape(n + 1, T, T)
+    with contextlib.ExitStack() as stack:
+        def upload(a):
+            d = stack.enter_context(hip.DeviceBuffer(max(a.nbytes, 16)))
+            d.put(a)
+            return d
+        d_blob, d_off = upload(blob), upload(offsets)
+        d_tiles = upload(np.full((n + 1, T, T), 0x5C, dtype=np.uint8))      # one tile of guard
+        d_dims, d_status = upload(np.full((n, 2), -7, np.int32)), upload(np.full(n, -7, np.int32))
+        hip.check(L.tmh_jpeg_decode_tiles_device(d_blob, d_off, n, d_tiles, d_dims,
+                                                 d_status, None))
+        tiles = d_tiles.get((n + 1, T, T), np.uint8)
         assert np.all(tiles[n] == 0x5C), "a write past the last tile"
-        return tiles[:n], d_dims.get().reshape(n, 2), d_status.get()
-    finally:
-        for d in (d_blob, d_off, d_tiles, d_dims, d_status):
-            d.free()
+        return tiles[:n], d_dims.get((n, 2), np.int32), d_status.get(n, np.int32)
 
 
 def test_decode_every_golden_in_one_call(L, goldens):
-    from tmlibrary_amd import hip
     files = [g[3] for g in goldens]
     tiles, dims, status = _decode_device(L, files)
     assert not status.any()
@@ -226,19 +197,16 @@ def test_status_cases_among_good_files(L, goldens):
 
 
 def test_decode_empty_list_and_bad_arguments(L):
-    from tmlibrary_amd import hip
     from tmlibrary_amd.workflow.pyramid import decode_jpeg_tiles
     assert decode_jpeg_tiles([]) == []
     off = np.zeros(1, dtype=np.int64)
     assert L.tmh_jpeg_decode_tiles(None, hip.ptr(off), 0, None, None, None) == 0
-    d_off = Dev(L, off)
-    try:
-        assert L.tmh_jpeg_decode_tiles_device(None, d_off.p, 0, None, None, None, None) == 0
-        assert L.tmh_jpeg_decode_tiles_device(None, d_off.p, 1, None, None, None, None) == hip.TMH_EINVAL
+    with hip.DeviceBuffer(max(off.nbytes, 16)) as d_off:
+        d_off.put(off)
+        assert L.tmh_jpeg_decode_tiles_device(None, d_off, 0, None, None, None, None) == 0
+        assert L.tmh_jpeg_decode_tiles_device(None, d_off, 1, None, None, None, None) == hip.TMH_EINVAL
         assert L.tmh_jpeg_decode_tiles_device(None, None, 0, None, None, None, None) == hip.TMH_EINVAL
-        assert L.tmh_jpeg_decode_tiles_device(None, d_off.p, -1, None, None, None, None) == hip.TMH_EINVAL
-    finally:
-        d_off.free()
+        assert L.tmh_jpeg_decode_tiles_device(None, d_off, -1, None, None, None, None) == hip.TMH_EINVAL
     blob, tile = np.zeros(8, np.uint8), np.full((T, T), 0x5C, np.uint8)
     dims, status = np.full(2, -7, np.int32), np.full(1, -7, np.int32)
     down = np.array([4, 2], dtype=np.int64)
@@ -264,7 +232,6 @@ def test_decode_jpeg_tiles_raises_with_index_and_status(L, goldens):
 def test_encoded_level_decode_equals_the_roundtrip(L, mixed):
     """The decoder over the encoder's blob: an independent path to the same
     pixels as the round trip pass."""
-    from tmlibrary_amd import hip
     from tmlibrary_amd.image import tiles_to_array
     from tmlibrary_amd.workflow.pyramid import EncodedLevel
     tiles, rows, cols, lh, lw, want = mixed

@@ -30,8 +30,9 @@ import numpy as np
 import pytest
 
 from oracle import corilla_oracle as orc
-from test_gpu_parity import Dev, check_order_stats, site_order_stats
-from util import assert_close_rel, dn_report
+from test_gpu_parity import check_order_stats, site_order_stats
+from tmlibrary_amd import hip
+from util import assert_close_rel, dn_report, keep  # noqa: F401 (keep: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +41,6 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def L():
-    from tmlibrary_amd import hip
     return hip.lib()
 
 
@@ -70,7 +70,6 @@ def test_bench_two_lanes():
 
 
 def _handle(L, H, W):
-    from tmlibrary_amd import hip
     from tmlibrary_amd.workflow.corilla.quantiles import quantile_table, stats_log10_lut
     lo, hi, gamma = quantile_table(H * W, np.linspace(0, 100, 100000))
     lut = stats_log10_lut()
@@ -81,10 +80,10 @@ def _handle(L, H, W):
 
 
 @pytest.mark.timeout(600)
-def test_corrector_tail_pending(L):
+def test_corrector_tail_pending(L, keep):
     import torch
 
-    from tmlibrary_amd import hip, synth
+    from tmlibrary_amd import synth
     from tmlibrary_amd.image import ZERO_LOG10
     H, W, n = 540, 640, 24
     npx = H * W
@@ -103,29 +102,29 @@ def test_corrector_tail_pending(L):
     hs = [_handle(L, H, W), _handle(L, H, W)]
     for h, sp in zip(hs, (sp1, sp2)):
         hip.check(L.tmh_stats_set_stream(h, sp))
-    d_in = [Dev(L, n * npx * 2) for _ in range(2)]
-    d_out = [Dev(L, n * npx * 2) for _ in range(2)]
+    d_in = [keep(hip.DeviceBuffer(n * npx * 2)) for _ in range(2)]
+    d_out = [keep(hip.DeviceBuffer(n * npx * 2)) for _ in range(2)]
     for j in range(2):
         d_in[j].put(sites[j])
-    planes = [[Dev(L, npx * 8) for _ in range(5)] for _ in range(2)]
+    planes = [[keep(hip.DeviceBuffer(npx * 8)) for _ in range(5)] for _ in range(2)]
     c = C.c_void_p()
     L.tmh_synchronize(None)
-    hip.check(L.tmh_corrector_create_device(planes[0][0].p, planes[0][1].p, H, W, 1, ZERO_LOG10,
+    hip.check(L.tmh_corrector_create_device(planes[0][0], planes[0][1], H, W, 1, ZERO_LOG10,
                                             spc, C.byref(c)))
     L.tmh_synchronize(None)
     cfgs = []
     for j, (h, sp) in enumerate(zip(hs, (sp1, sp2))):  # no host synchronisation in between
         mean, std, smean, sstd, tmp = planes[j]
         hip.check(L.tmh_stats_reset(h))
-        hip.check(L.tmh_stats_update_welford_device(h, d_in[j].p, n, 1, sp))
-        hip.check(L.tmh_stats_finalize_device(h, mean.p, std.p, sp))
-        hip.check(L.tmh_smooth_f64_device(mean.p, smean.p, tmp.p, H, W, 5.0, sp))
-        hip.check(L.tmh_smooth_f64_device(std.p, sstd.p, tmp.p, H, W, 5.0, sp))
-        hip.check(L.tmh_corrector_update_device(c, smean.p, sstd.p, sp))
+        hip.check(L.tmh_stats_update_welford_device(h, d_in[j], n, 1, sp))
+        hip.check(L.tmh_stats_finalize_device(h, mean, std, sp))
+        hip.check(L.tmh_smooth_f64_device(mean, smean, tmp, H, W, 5.0, sp))
+        hip.check(L.tmh_smooth_f64_device(std, sstd, tmp, H, W, 5.0, sp))
+        hip.check(L.tmh_corrector_update_device(c, smean, sstd, sp))
         # the corrected pass on the corrector's own stream: cross-stream, so
         # this job's tail goes to h's tail stream and the pass of job 2 is
         # queued while job 1's tail is pending
-        hip.check(L.tmh_correct_u16_hist_device(c, h, d_in[j].p, d_out[j].p, n, -1, -1, spc))
+        hip.check(L.tmh_correct_u16_hist_device(c, h, d_in[j], d_out[j], n, -1, -1, spc))
         fc = C.c_int()
         hip.check(L.tmh_stats_job_choice(h, None, None, C.byref(fc)))
         cfgs.append(fc.value)
@@ -150,7 +149,7 @@ def test_corrector_tail_pending(L):
             hip.check(L.tmh_stats_site_histogram(h, i, hip.ptr(sh)))
             assert np.array_equal(sh.astype(np.uint64), orc.histogram_u16(sites[j][i])), (j, i)
         check_order_stats([sites[j][i] for i in idx], site_order_stats(L, h, idx, 100000))
-        out = d_out[j].get(np.uint16, sites[j].shape)
+        out = d_out[j].get(sites[j].shape, np.uint16)
         sm_ref, ss_ref = orc.smooth_reflect(ref.mean, 5), orc.smooth_reflect(ref.std, 5)
         for i in (0, n - 1):
             worst, flips, _ = dn_report(out[i], orc.correct_illumination(sites[j][i], sm_ref, ss_ref))
@@ -158,5 +157,3 @@ def test_corrector_tail_pending(L):
     L.tmh_corrector_destroy(c)
     for h in hs:
         L.tmh_stats_destroy(h)
-    for b in d_in + d_out + planes[0] + planes[1]:
-        b.free()

@@ -1,13 +1,16 @@
 """GPU parity: the HIP path (through the C-ABI) vs the oracle and the golden
 fixtures.  Bars (BASELINE.json north_star): mean/std 1e-6 relative,
 percentiles and histograms bit-exact, corrected uint16 within +-1 DN."""
+import contextlib
 import ctypes as C
 import hashlib
 
 import numpy as np
 import pytest
 
+from tmlibrary_amd import hip
 from util import assert_close_rel, assert_dn, dn_report, load_golden
+from util import keep  # noqa: F401 (a fixture)
 from oracle import corilla_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -18,36 +21,12 @@ STATS_CASES = ["stats_small", "stats_medium", "stats_extremes", "stats_single", 
 
 @pytest.fixture(scope="module")
 def L():
-    from tmlibrary_amd import hip
     return hip.lib()
-
-
-class Dev:
-    """Raw device buffer via the C-ABI helpers (no torch needed)."""
-
-    def __init__(self, L, nbytes):
-        self.L = L
-        self.p = C.c_void_p()
-        assert L.tmh_malloc_device(C.byref(self.p), max(int(nbytes), 1)) == 0
-        self.nbytes = nbytes
-
-    def put(self, a):
-        a = np.ascontiguousarray(a)
-        assert self.L.tmh_memcpy(self.p, a.ctypes.data, a.nbytes, 0, None) == 0
-
-    def get(self, dtype, shape):
-        out = np.empty(shape, dtype)
-        assert self.L.tmh_memcpy(out.ctypes.data, self.p, out.nbytes, 1, None) == 0
-        return out
-
-    def free(self):
-        self.L.tmh_free_device(self.p)
 
 
 def site_order_stats(L, h, sites, Q):
     """(previous, next) order statistics of the given sites of the handle's
     last batch, decoded from the device's (compact or dense) storage."""
-    from tmlibrary_amd import hip
     res = []
     for i in sites:
         a, b = np.empty(Q, np.uint16), np.empty(Q, np.uint16)
@@ -99,7 +78,6 @@ def test_stats_vs_golden(L, name, batch):
 
 
 def test_site_histograms_bit_exact(L):
-    from tmlibrary_amd import hip
     g = load_golden("stats_extremes")
     sites = list(g["sites"])
     st = run_stats(sites, batch=64, flags=hip.TMH_STATS_KEEP_SITE_HIST)
@@ -262,32 +240,29 @@ def test_smooth_small_planes(L, shape):
 
 @pytest.mark.parametrize("shape,sigma", [((2160, 2560), 5.0), ((37, 53), 5.0), ((96, 128), 2.0),
                                          ((8, 700), 40.0)])
-def test_smooth2_equals_two_planes(L, shape, sigma):
+def test_smooth2_equals_two_planes(L, keep, shape, sigma):
     """tmh_smooth2_f64_device (a job's mean and std in one launch per axis)
     is bit-identical to two tmh_smooth_f64_device calls, for the radius-20
     strip kernel, the generic axis-0 kernel and the wide (radius > 128)
     axis-1 kernel."""
-    from tmlibrary_amd import hip
     H, W = shape
     rng = np.random.default_rng(H * 7 + W)
     a = rng.random(shape) * 3.0 + 0.5
     b = rng.random(shape) * 0.2 + 0.01
-    bufs = [Dev(L, H * W * 8) for _ in range(8)]
+    bufs = [keep(hip.DeviceBuffer(H * W * 8)) for _ in range(8)]
     ia, ib, o1a, o1b, o2a, o2b, t0, t1 = bufs
     ia.put(a)
     ib.put(b)
-    hip.check(L.tmh_smooth_f64_device(ia.p, o1a.p, t0.p, H, W, sigma, None))
-    hip.check(L.tmh_smooth_f64_device(ib.p, o1b.p, t0.p, H, W, sigma, None))
-    hip.check(L.tmh_smooth2_f64_device(ia.p, ib.p, o2a.p, o2b.p, t0.p, t1.p, H, W, sigma, None))
+    hip.check(L.tmh_smooth_f64_device(ia, o1a, t0, H, W, sigma, None))
+    hip.check(L.tmh_smooth_f64_device(ib, o1b, t0, H, W, sigma, None))
+    hip.check(L.tmh_smooth2_f64_device(ia, ib, o2a, o2b, t0, t1, H, W, sigma, None))
     L.tmh_synchronize(None)
-    ra, rb = o1a.get(np.float64, shape), o1b.get(np.float64, shape)
-    assert np.array_equal(o2a.get(np.float64, shape), ra)
-    assert np.array_equal(o2b.get(np.float64, shape), rb)
+    ra, rb = o1a.get(shape, np.float64), o1b.get(shape, np.float64)
+    assert np.array_equal(o2a.get(shape, np.float64), ra)
+    assert np.array_equal(o2b.get(shape, np.float64), rb)
     assert np.allclose(ra, orc.smooth_reflect(a, sigma), rtol=1e-10, atol=1e-13)
     # scratch aliasing an input or output is refused
-    assert L.tmh_smooth2_f64_device(ia.p, ib.p, o2a.p, o2b.p, ia.p, t1.p, H, W, sigma, None) == -22
-    for d in bufs:
-        d.free()
+    assert L.tmh_smooth2_f64_device(ia, ib, o2a, o2b, ia, t1, H, W, sigma, None) == -22
 
 
 def test_corrector_cache_sees_in_place_writes(L):
@@ -427,16 +402,15 @@ def test_fullsize_two_sites(L):
     print("fullsize corrected bit-identical to reference:", exact)
 
 
-def test_device_path_large_batch(L):
+def test_device_path_large_batch(L, keep):
     """Sites generated in HBM, one update_device call, vs the oracle on a copy."""
-    from tmlibrary_amd import hip
     from tmlibrary_amd.workflow.corilla.quantiles import quantile_table, stats_log10_lut
     H, W, n = 540, 640, 40
     npx = H * W
-    d = Dev(L, n * npx * 2)
-    hip.check(L.tmh_synth_sites_device(d.p, n, H, W, 99, 0, 0, hip.TMH_SYNTH_STANDARD, None))
+    d = keep(hip.DeviceBuffer(n * npx * 2))
+    hip.check(L.tmh_synth_sites_device(d, n, H, W, 99, 0, 0, hip.TMH_SYNTH_STANDARD, None))
     L.tmh_synchronize(None)
-    sites = d.get(np.uint16, (n, H, W))
+    sites = d.get((n, H, W), np.uint16)
     from tmlibrary_amd.synth import synth_exact_host  # the device generator's host twin
     for i in (0, n - 1):
         assert np.array_equal(sites[i], synth_exact_host(H, W, 99, 0, i))
@@ -446,7 +420,7 @@ def test_device_path_large_batch(L):
     h = C.c_void_p()
     hip.check(L.tmh_stats_create(H, W, 100000, hip.ptr(lo), hip.ptr(hi), hip.ptr(gamma),
                                  hip.ptr(lut), 8, 0, C.byref(h)))
-    hip.check(L.tmh_stats_update_device(h, d.p, n, 1, None))
+    hip.check(L.tmh_stats_update_device(h, d, n, 1, None))
     mean = np.empty((H, W))
     std = np.empty((H, W))
     acc = np.empty(100000)
@@ -458,13 +432,11 @@ def test_device_path_large_batch(L):
     assert_close_rel(std, ref.std)
     assert np.array_equal(acc, ref.percentile_sums)
     L.tmh_stats_destroy(h)
-    d.free()
 
 
-def test_deferred_chain_and_merge_single_gpu(L):
+def test_deferred_chain_and_merge_single_gpu(L, keep):
     """Two handles = two 'ranks' on one GPU: Chan merge + ordered percentile
     chain reproduce the single-handle result (mean/std 1e-6, pct bit-exact)."""
-    from tmlibrary_amd import hip
     from tmlibrary_amd.workflow.corilla.quantiles import quantile_table, stats_log10_lut
     sites = np.stack(load_golden("stats_medium")["sites"])
     n, H, W = sites.shape
@@ -484,27 +456,27 @@ def test_deferred_chain_and_merge_single_gpu(L):
     for h, p in zip(hs, parts):
         hip.check(L.tmh_stats_update(h, hip.ptr(np.ascontiguousarray(p)), len(p), 1, None))
     # all-reduce emulated by host sums of the device buffers
-    bufs = [Dev(L, npx * 8) for _ in hs]
+    bufs = [keep(hip.DeviceBuffer(npx * 8)) for _ in hs]
     for h, b in zip(hs, bufs):
-        hip.check(L.tmh_stats_merge_stage1(h, b.p, None))
+        hip.check(L.tmh_stats_merge_stage1(h, b, None))
     L.tmh_synchronize(None)
-    s1 = sum(b.get(np.float64, npx) for b in bufs)
-    sum_dev = Dev(L, npx * 8)
+    s1 = sum(b.get(npx, np.float64) for b in bufs)
+    sum_dev = keep(hip.DeviceBuffer(npx * 8))
     sum_dev.put(s1)
     for h, b in zip(hs, bufs):
-        hip.check(L.tmh_stats_merge_stage2(h, sum_dev.p, n, b.p, None))
+        hip.check(L.tmh_stats_merge_stage2(h, sum_dev, n, b, None))
     L.tmh_synchronize(None)
-    s2 = sum(b.get(np.float64, npx) for b in bufs)
+    s2 = sum(b.get(npx, np.float64) for b in bufs)
     sum_dev.put(s2)
     for h in hs:
-        hip.check(L.tmh_stats_merge_stage3(h, n, sum_dev.p, None))
-    acc = Dev(L, 100000 * 8)
+        hip.check(L.tmh_stats_merge_stage3(h, n, sum_dev, None))
+    acc = keep(hip.DeviceBuffer(100000 * 8))
     acc.put(np.zeros(100000))
     for h in hs:  # rank order; each handle has its own stream, so wait in between
-        hip.check(L.tmh_stats_pct_accumulate(h, acc.p, None))
+        hip.check(L.tmh_stats_pct_accumulate(h, acc, None))
         L.tmh_synchronize(None)
     for h in hs:
-        hip.check(L.tmh_stats_set_pct_sum(h, acc.p, None))
+        hip.check(L.tmh_stats_set_pct_sum(h, acc, None))
     L.tmh_synchronize(None)
     ref = orc.run_illumstats(list(sites))
     for h in hs:
@@ -519,12 +491,9 @@ def test_deferred_chain_and_merge_single_gpu(L):
         assert_close_rel(std, ref.std)
         assert np.array_equal(pct, ref.percentile_sums)
         L.tmh_stats_destroy(h)
-    for b in bufs + [sum_dev, acc]:
-        b.free()
 
 
 def test_profile_counters(L):
-    from tmlibrary_amd import hip
     L.tmh_profile_enable(1)
     L.tmh_profile_reset()
     run_stats(list(load_golden("stats_small")["sites"]), batch=8)._finalize()
@@ -621,7 +590,6 @@ def _fused_job(L, sites, clip=(-1, -1), q=None, cfg=-1):
     """Split pipeline through the C-ABI: Welford-only update -> finalize ->
     smooth -> corrector -> fused correct+histogram (cfg: TMH_OPT_FUSED_CONFIG,
     -1 = the automatic choice).  Returns host results."""
-    from tmlibrary_amd import hip
     from tmlibrary_amd.image import ZERO_LOG10
     from tmlibrary_amd.workflow.corilla.quantiles import quantile_table, stats_log10_lut
     n, H, W = sites.shape
@@ -635,43 +603,43 @@ def _fused_job(L, sites, clip=(-1, -1), q=None, cfg=-1):
                                  hip.ptr(lut), 4, hip.TMH_STATS_KEEP_SITE_HIST, C.byref(h)))
     if cfg != -1:
         hip.check(L.tmh_stats_set_option(h, hip.TMH_OPT_FUSED_CONFIG, cfg))
-    d_in, d_out = Dev(L, sites.nbytes), Dev(L, sites.nbytes)
-    d_in.put(sites)
-    planes = [Dev(L, npx * 8) for _ in range(5)]
-    mean, std, smean, sstd, tmp = planes
-    hip.check(L.tmh_stats_update_welford_device(h, d_in.p, n, 1, None))
-    hip.check(L.tmh_stats_finalize_device(h, mean.p, std.p, None))
-    L.tmh_synchronize(None)
-    hip.check(L.tmh_smooth_f64_device(mean.p, smean.p, tmp.p, H, W, 5.0, None))
-    hip.check(L.tmh_smooth_f64_device(std.p, sstd.p, tmp.p, H, W, 5.0, None))
-    L.tmh_synchronize(None)
-    c = C.c_void_p()
-    hip.check(L.tmh_corrector_create_device(smean.p, sstd.p, H, W, 1, ZERO_LOG10, None, C.byref(c)))
-    hip.check(L.tmh_correct_u16_hist_device(c, h, d_in.p, d_out.p, n, clip[0], clip[1], None))
-    L.tmh_synchronize(None)
-    acc = np.empty(Q)
-    nn = C.c_int64()
-    m_h = np.empty((H, W))
-    s_h = np.empty((H, W))
-    hist = np.empty(65536, np.uint64)
-    hip.check(L.tmh_stats_finalize(h, C.byref(nn), hip.ptr(m_h), hip.ptr(s_h), hip.ptr(acc),
-                                   hip.ptr(hist)))
-    site_h = []
-    for i in range(n):
-        sh = np.empty(65536, np.uint32)
-        hip.check(L.tmh_stats_site_histogram(h, i, hip.ptr(sh)))
-        site_h.append(sh)
-    out = d_out.get(np.uint16, sites.shape)
-    pc, wb, fc = (C.c_uint32 * 3)(), C.c_int(), C.c_int()
-    hip.check(L.tmh_stats_job_choice(h, pc, C.byref(wb), C.byref(fc)))
-    res = dict(n=nn.value, mean=m_h, std=s_h, acc=acc, hist=hist, site_hist=site_h, out=out,
-               fused_cfg=fc.value, welford_bright=wb.value,
-               smean=smean.get(np.float64, (H, W)), sstd=sstd.get(np.float64, (H, W)),
-               order_stats=site_order_stats(L, h, range(n), Q))
-    L.tmh_corrector_destroy(c)
-    L.tmh_stats_destroy(h)
-    for b in planes + [d_in, d_out]:
-        b.free()
+    with contextlib.ExitStack() as stack:
+        keep = stack.enter_context
+        d_in, d_out = keep(hip.DeviceBuffer(sites.nbytes)), keep(hip.DeviceBuffer(sites.nbytes))
+        d_in.put(sites)
+        planes = [keep(hip.DeviceBuffer(npx * 8)) for _ in range(5)]
+        mean, std, smean, sstd, tmp = planes
+        hip.check(L.tmh_stats_update_welford_device(h, d_in, n, 1, None))
+        hip.check(L.tmh_stats_finalize_device(h, mean, std, None))
+        L.tmh_synchronize(None)
+        hip.check(L.tmh_smooth_f64_device(mean, smean, tmp, H, W, 5.0, None))
+        hip.check(L.tmh_smooth_f64_device(std, sstd, tmp, H, W, 5.0, None))
+        L.tmh_synchronize(None)
+        c = C.c_void_p()
+        hip.check(L.tmh_corrector_create_device(smean, sstd, H, W, 1, ZERO_LOG10, None, C.byref(c)))
+        hip.check(L.tmh_correct_u16_hist_device(c, h, d_in, d_out, n, clip[0], clip[1], None))
+        L.tmh_synchronize(None)
+        acc = np.empty(Q)
+        nn = C.c_int64()
+        m_h = np.empty((H, W))
+        s_h = np.empty((H, W))
+        hist = np.empty(65536, np.uint64)
+        hip.check(L.tmh_stats_finalize(h, C.byref(nn), hip.ptr(m_h), hip.ptr(s_h), hip.ptr(acc),
+                                       hip.ptr(hist)))
+        site_h = []
+        for i in range(n):
+            sh = np.empty(65536, np.uint32)
+            hip.check(L.tmh_stats_site_histogram(h, i, hip.ptr(sh)))
+            site_h.append(sh)
+        out = d_out.get(sites.shape, np.uint16)
+        pc, wb, fc = (C.c_uint32 * 3)(), C.c_int(), C.c_int()
+        hip.check(L.tmh_stats_job_choice(h, pc, C.byref(wb), C.byref(fc)))
+        res = dict(n=nn.value, mean=m_h, std=s_h, acc=acc, hist=hist, site_hist=site_h, out=out,
+                   fused_cfg=fc.value, welford_bright=wb.value,
+                   smean=smean.get((H, W), np.float64), sstd=sstd.get((H, W), np.float64),
+                   order_stats=site_order_stats(L, h, range(n), Q))
+        L.tmh_corrector_destroy(c)
+        L.tmh_stats_destroy(h)
     return res
 
 
@@ -871,7 +839,6 @@ def test_scatter_round_mask_edges(L, shape):
     scalar path (345): every site's order statistics for all 100,000
     quantiles and its histogram, the percentile sums and the pooled histogram,
     bit for bit, with the zero-maintained slab reused after high sites."""
-    from tmlibrary_amd import hip
     sites = round_mask_edge_sites(shape)
     hists = [orc.histogram_u16(s) for s in sites]
 
@@ -912,7 +879,6 @@ def test_welford_site_parts(L, parts):
     launch policy picks at 2160x2560): parts merged in order, then into the
     state of the previous launch -- mean/std still within the 1e-6 bar, and
     var = M2 / (n - 1) from the device (stats.py:94-102)."""
-    from tmlibrary_amd import hip
     from tmlibrary_amd.image import ChannelImage
     from tmlibrary_amd.synth import synth_sites_host
     from tmlibrary_amd.workflow.corilla.stats import OnlineStatistics
@@ -929,10 +895,9 @@ def test_welford_site_parts(L, parts):
     st.close()
 
 
-def test_pipelined_chain_ranges_bit_exact(L):
+def test_pipelined_chain_ranges_bit_exact(L, keep):
     """tmh_stats_pct_accumulate_range over quantile chunks, chunk-major across
     two 'ranks' (the pipelined chain's order), equals the sequential sum."""
-    from tmlibrary_amd import hip
     from tmlibrary_amd.workflow.corilla.quantiles import quantile_table, stats_log10_lut
     from tmlibrary_amd.workflow.corilla.sharded import chain_chunks
     sites = np.stack(load_golden("stats_medium")["sites"])
@@ -949,17 +914,16 @@ def test_pipelined_chain_ranges_bit_exact(L):
         hip.check(L.tmh_stats_update(h, hip.ptr(np.ascontiguousarray(p)), len(p), 1, None))
         hs.append(h)
     L.tmh_synchronize(None)
-    acc = Dev(L, Q * 8)
+    acc = keep(hip.DeviceBuffer(Q * 8))
     acc.put(np.zeros(Q))
     for q0, qn in chain_chunks(Q, 2, chunks=7) + [(Q, 0)]:
         for h in hs:
-            hip.check(L.tmh_stats_pct_accumulate_range(h, C.c_void_p(acc.p.value + 8 * q0), q0, qn,
+            hip.check(L.tmh_stats_pct_accumulate_range(h, acc.at(8 * q0), q0, qn,
                                                        None))
             L.tmh_synchronize(None)
-    got = acc.get(np.float64, Q)
+    got = acc.get(Q, np.float64)
     ref = orc.run_illumstats(list(sites))
     assert np.array_equal(got, ref.percentile_sums)
-    assert hip.lib().tmh_stats_pct_accumulate_range(hs[0], acc.p, Q - 2, 4, None) != 0
+    assert hip.lib().tmh_stats_pct_accumulate_range(hs[0], acc, Q - 2, 4, None) != 0
     for h in hs:
         L.tmh_stats_destroy(h)
-    acc.free()

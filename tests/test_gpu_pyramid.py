@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 import pyramid_literal as lit
+from tmlibrary_amd import hip
+from util import keep  # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 T = 256
@@ -16,7 +18,6 @@ T = 256
 
 @pytest.fixture(scope="module")
 def L():
-    from tmlibrary_amd import hip
     return hip.lib()
 
 
@@ -36,30 +37,6 @@ def cases():
             cache[name] = (g, sites, want, missing)
         return cache[name]
     return get
-
-
-class Dev(object):
-    """A device buffer holding a copy of ``a`` (or ``nbytes`` of ``fill``)."""
-
-    def __init__(self, L, a=None, nbytes=None, fill=0xAA):
-        from tmlibrary_amd import hip
-        self.L, self.hip = L, hip
-        if a is None:
-            a = np.full(nbytes, fill, dtype=np.uint8)
-        a = np.ascontiguousarray(a)
-        self.nbytes = a.nbytes
-        self.p = C.c_void_p()
-        hip.check(L.tmh_malloc_device(C.byref(self.p), a.nbytes))
-        hip.check(L.tmh_memcpy(self.p, hip.ptr(a), a.nbytes, 0, None))
-
-    def get(self, shape, dtype=np.uint8):
-        out = np.empty(shape, dtype=dtype)
-        assert out.nbytes == self.nbytes
-        self.hip.check(self.L.tmh_memcpy(self.hip.ptr(out), self.p, out.nbytes, 1, None))
-        return out
-
-    def free(self):
-        self.L.tmh_free_device(self.p)
 
 
 def _stitch(level):
@@ -92,7 +69,6 @@ def test_base_tiles_match_literal_loop(L, cases, name):
 def test_tiles_base_host_form_any_table_order(L, cases):
     """tmh_tiles_base (host pointers) with the table shuffled: the entry
     point sorts by tile itself."""
-    from tmlibrary_amd import hip
     from tmlibrary_amd.workflow.pyramid import plan_base_tiles
     g, sites, want, _ = cases("two_wells")
     table = plan_base_tiles(g)
@@ -108,7 +84,6 @@ def test_tiles_base_host_form_any_table_order(L, cases):
 # ---- shrink -------------------------------------------------------------------------
 
 def _shrink_host_form(L, level, last_h, last_w, fill=0xAA):
-    from tmlibrary_amd import hip
     rows, cols = level.shape[:2]
     out = np.full(((rows + 1) // 2, (cols + 1) // 2, T, T), fill, dtype=np.uint8)
     oh, ow = C.c_int(-1), C.c_int(-1)
@@ -119,19 +94,15 @@ def _shrink_host_form(L, level, last_h, last_w, fill=0xAA):
 
 
 def _shrink_device_form(L, level, last_h, last_w, fill=0xAA):
-    from tmlibrary_amd import hip
     rows, cols = level.shape[:2]
     oshape = ((rows + 1) // 2, (cols + 1) // 2, T, T)
-    src, dst = Dev(L, level), Dev(L, nbytes=int(np.prod(oshape)), fill=fill)
-    try:
+    with hip.DeviceBuffer.from_array(level) as src, \
+            hip.DeviceBuffer.from_array(np.full(oshape, fill, np.uint8)) as dst:
         oh, ow = C.c_int(-1), C.c_int(-1)
-        hip.check(L.tmh_pyramid_shrink2_device(src.p, rows, cols, last_h, last_w, dst.p,
+        hip.check(L.tmh_pyramid_shrink2_device(src, rows, cols, last_h, last_w, dst,
                                                C.byref(oh), C.byref(ow), None))
         hip.check(L.tmh_synchronize(None))
-        return dst.get(oshape), oh.value, ow.value
-    finally:
-        src.free()
-        dst.free()
+        return dst.get(oshape, np.uint8), oh.value, ow.value
 
 
 def test_shrink_rounding_every_block(L):
@@ -262,10 +233,9 @@ def test_whole_pyramid_two_wells(L, cases):
 
 # ---- device-resident path ------------------------------------------------------------------
 
-def test_chain_output_feeds_the_pyramid_on_the_device(L):
+def test_chain_output_feeds_the_pyramid_on_the_device(L, keep):
     """tmh_correct_chain_u8_device's device output goes straight into
     build_pyramid; same pyramid as from the host copy of that output."""
-    from tmlibrary_amd import hip
     from tmlibrary_amd.image import Corrector, align_window
     from tmlibrary_amd.synth import synth_sites_host
     from tmlibrary_amd.workflow.pyramid import build_pyramid
@@ -279,12 +249,13 @@ def test_chain_output_feeds_the_pyramid_on_the_device(L):
         [align_window((H, W), 3 - i, i - 2, 4, 4, 4, 4, crop=False)[0] for i in range(n)],
         dtype=hip.WINDOW_DTYPE))
     corr = Corrector(mean, std)
-    d_in, d_out = Dev(L, raw), Dev(L, nbytes=n * H * W)
+    d_in = keep(hip.DeviceBuffer.from_array(raw))
+    d_out = keep(hip.DeviceBuffer.from_array(np.full(n * H * W, 0xAA, np.uint8)))
     try:
-        hip.check(L.tmh_correct_chain_u8_device(corr._h, d_in.p, d_out.p, n, hip.ptr(win), 110, 900,
+        hip.check(L.tmh_correct_chain_u8_device(corr._h, d_in, d_out, n, hip.ptr(win), 110, 900,
                                                 None))
-        with build_pyramid(g, d_out.p) as from_device:
-            host_copy = d_out.get((n, H, W))
+        with build_pyramid(g, d_out.ptr) as from_device:
+            host_copy = d_out.get((n, H, W), np.uint8)
             assert len(np.unique(host_copy)) > 100      # a real image, not a constant
             with build_pyramid(g, host_copy) as from_host:
                 for z in range(from_host.depth):
@@ -292,25 +263,22 @@ def test_chain_output_feeds_the_pyramid_on_the_device(L):
             want, _ = lit.literal_base_level(g, host_copy)
             assert np.array_equal(from_device.level(from_device.depth - 1), _stitch(want))
     finally:
-        d_in.free()
-        d_out.free()
         corr.close()
 
 
 # ---- argument errors --------------------------------------------------------------------------
 
 def test_argument_errors_launch_nothing(L):
-    from tmlibrary_amd import hip
     n, H, W, rows, cols = 2, 300, 420, 2, 2
-    sites = Dev(L, nbytes=n * H * W, fill=7)
-    tiles = Dev(L, nbytes=rows * cols * T * T, fill=0xAA)
-    small = Dev(L, nbytes=T * T, fill=0xAA)
+    sites = hip.DeviceBuffer.from_array(np.full(n * H * W, 7, np.uint8))
+    tiles = hip.DeviceBuffer.from_array(np.full(rows * cols * T * T, 0xAA, np.uint8))
+    small = hip.DeviceBuffer.from_array(np.full(T * T, 0xAA, np.uint8))
     ok = (1, 1, 10, 20, 30, 40, 50, 60)
 
     def table(*recs):
         return np.array(list(recs), dtype=hip.TILE_RECT_DTYPE)
 
-    def base(sites_p=sites.p, n_sites=n, h=H, w=W, recs=table(ok), n_rects=None, tiles_p=tiles.p,
+    def base(sites_p=sites, n_sites=n, h=H, w=W, recs=table(ok), n_rects=None, tiles_p=tiles,
              tr=rows, tc=cols):
         rp = None if recs is None else hip.ptr(recs)
         nr = (0 if recs is None else len(recs)) if n_rects is None else n_rects
@@ -323,7 +291,7 @@ def test_argument_errors_launch_nothing(L):
 
     lh, lw = C.c_int(), C.c_int()
 
-    def shrink(src=tiles.p, r=rows, c=cols, h=T, w=T, dst=small.p, ph=C.byref(lh), pw=C.byref(lw)):
+    def shrink(src=tiles, r=rows, c=cols, h=T, w=T, dst=small, ph=C.byref(lh), pw=C.byref(lw)):
         return L.tmh_pyramid_shrink2_device(src, r, c, h, w, dst, ph, pw, None)
 
     bad = {
@@ -356,26 +324,23 @@ def test_argument_errors_launch_nothing(L):
         "shrink cols negative": lambda: shrink(c=-2),
         "shrink last height 0": lambda: shrink(h=0),
         "shrink last width 257": lambda: shrink(w=257),
-        "shrink in place": lambda: shrink(dst=tiles.p),
+        "shrink in place": lambda: shrink(dst=tiles),
     }
-    try:
+    with sites, tiles, small:
         for name, call in bad.items():
             assert call() == hip.TMH_EINVAL, name
             assert len(L.tmh_last_error()) > 0, name
         hip.check(L.tmh_synchronize(None))
-        assert np.all(tiles.get((rows * cols * T * T,)) == 0xAA), "a refused call wrote tiles"
-        assert np.all(small.get((T * T,)) == 0xAA), "a refused call wrote a level"
+        assert np.all(tiles.get(rows * cols * T * T, np.uint8) == 0xAA), "a refused call wrote tiles"
+        assert np.all(small.get(T * T, np.uint8) == 0xAA), "a refused call wrote a level"
         # the same calls with good arguments do run
         assert base() == hip.TMH_OK
-        got = tiles.get((rows * cols, T, T))
+        got = tiles.get((rows * cols, T, T), np.uint8)
         want = np.zeros_like(got)
         want[1, 30:80, 40:100] = 7
         assert np.array_equal(got, want)
         assert shrink() == hip.TMH_OK and (lh.value, lw.value) == (T, T)
         hip.check(L.tmh_synchronize(None))
-        assert np.array_equal(small.get((T, T)),
+        assert np.array_equal(small.get((T, T), np.uint8),
                               lit.shrink_even(np.vstack([np.hstack([got[0], got[1]]),
                                                          np.hstack([got[2], got[3]])])))
-    finally:
-        for d in (sites, tiles, small):
-            d.free()

@@ -1,10 +1,20 @@
 """Shared test helpers (fixture loading, tolerance checks)."""
+import contextlib
 import os
 
 import numpy as np
+import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(REPO, "tests", "golden")
+
+
+@pytest.fixture
+def keep():
+    """``keep(buffer)`` returns the ``hip.DeviceBuffer`` and frees it when the test
+    ends, passed or failed.  A module that uses it imports it by name."""
+    with contextlib.ExitStack() as stack:
+        yield stack.enter_context
 
 
 def load_golden(name):

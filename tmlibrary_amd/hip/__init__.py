@@ -323,6 +323,82 @@ def ptr_or_null(a):
     return None if a is None else ptr(a)
 
 
+class DeviceBuffer(object):
+    """``nbytes`` of raw device memory, owned: the Python counterpart of ``DBuf``
+    (csrc/abi_internal.h).  Freed by ``free()``, at the end of a ``with`` block or
+    with the object.  It passes as an argument wherever ``SIGNATURES`` says
+    ``c_void_p``.  Exactly ``nbytes`` are allocated; none at all gives a NULL
+    ``ptr`` (``ptr.value is None``).  ``value`` is the address as ``ptr.value``
+    gives it, so code written for a ``c_void_p`` reads it alike.  ``put`` / ``get``
+    return when the copy is complete."""
+
+    def __init__(self, nbytes):
+        self.ptr = C.c_void_p()
+        self.nbytes = int(nbytes)
+        self._freed = False
+        if self.nbytes < 0:
+            raise ValueError("a buffer of %d bytes" % self.nbytes)
+        self._lib = lib()    # the free goes to the library that allocated
+        check(self._lib.tmh_malloc_device(C.byref(self.ptr), self.nbytes))
+
+    @classmethod
+    def from_array(cls, a, stream=None):
+        a = np.ascontiguousarray(a)
+        buf = cls(a.nbytes)
+        try:
+            buf.put(a, stream=stream)
+        except BaseException:
+            buf.free()
+            raise
+        return buf
+
+    @property
+    def _as_parameter_(self):
+        return self.ptr
+
+    @property
+    def value(self):
+        return self.ptr.value
+
+    def at(self, offset, nbytes=0):
+        """The address ``offset`` bytes into the buffer, with ``nbytes`` behind it."""
+        if self._freed:
+            raise ValueError("buffer is freed")
+        if not 0 <= offset <= offset + nbytes <= self.nbytes:
+            raise ValueError("bytes %d to %d of a buffer of %d"
+                             % (offset, offset + nbytes, self.nbytes))
+        return C.c_void_p((self.ptr.value or 0) + offset)
+
+    def put(self, a, offset=0, stream=None):
+        a = np.ascontiguousarray(a)
+        check(self._lib.tmh_memcpy(self.at(offset, a.nbytes), ptr(a), a.nbytes, 0, stream))
+
+    def get(self, shape, dtype, offset=0, stream=None):
+        out = np.empty(shape, dtype=dtype)
+        check(self._lib.tmh_memcpy(ptr(out), self.at(offset, out.nbytes), out.nbytes, 1, stream))
+        return out
+
+    def free(self):
+        if self._freed:
+            return
+        self._freed = True
+        p, self.ptr = self.ptr, C.c_void_p()
+        if p.value:
+            self._lib.tmh_free_device(p)    # as in DBuf's destructor, its status is dropped
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:    # the library may be gone at interpreter exit
+            pass
+
+
 def available() -> bool:
     try:
         lib()

@@ -27,6 +27,21 @@ from tmlibrary_amd import hip
 from tmlibrary_amd.models.file import RawChunksUnsupported, read_raw_chunks
 
 
+def grow(slot, name, n, dtype, device=None):
+    """``slot[name]``, a tensor of at least ``n`` elements: one of 1.25 x ``n`` replaces
+    it when it is missing or smaller.  On ``device``, or pinned host memory for None."""
+    import torch
+    t = slot.get(name)
+    if t is None or t.numel() < n:
+        n = max(int(n * 1.25), 1)
+        if device is None:
+            t = torch.empty(n, dtype=dtype, pin_memory=True)
+        else:
+            t = torch.empty(n, dtype=dtype, device=device)
+        slot[name] = t
+    return t
+
+
 class DeviceChunkDecoder(object):
     """Inflate blocks of channel image files into device site buffers.
 
@@ -49,18 +64,6 @@ class DeviceChunkDecoder(object):
         # host seconds: waiting for a slot's previous block, reading raw chunks
         # (libhdf5 metadata + pread), the whole decode() call
         self.times = {"slot_wait": 0.0, "read": 0.0, "call": 0.0}
-
-    def _grow(self, slot, name, n, dtype, pinned=False):
-        torch = self.torch
-        t = slot.get(name)
-        if t is None or t.numel() < n:
-            n = max(int(n * 1.25), 1)
-            if pinned:
-                t = torch.empty(n, dtype=dtype, pin_memory=True)
-            else:
-                t = torch.empty(n, dtype=dtype, device=self.device)
-            slot[name] = t
-        return t
 
     def decode(self, paths, out_ptr, n_out=None, expect=None):
         """Decode ``paths`` into the device buffer at ``out_ptr`` ([n, H, W] of
@@ -97,7 +100,7 @@ class DeviceChunkDecoder(object):
                 raise RawChunksUnsupported("%d-byte pixels in a %d-byte job" % (es, ees))
         n = len(table)
         if hb is None or blob.ctypes.data != hb.data_ptr():  # grown: pin the new size
-            hb = self._grow(slot, "h_blob", blob.nbytes, torch.uint8, pinned=True)
+            hb = grow(slot, "h_blob", blob.nbytes, torch.uint8)
             hb.numpy()[:blob.nbytes] = blob
             slot["h_blob"] = hb
         tb = table.view(np.uint8).reshape(-1)
@@ -106,14 +109,14 @@ class DeviceChunkDecoder(object):
             ht = torch.empty(max(int(n * 1.25), 1) * esz, dtype=torch.uint8, pin_memory=True)
             ht.numpy()[:tb.nbytes] = tb
             slot["h_tab"] = ht
-        d_src = self._grow(slot, "d_src", blob.nbytes + 16, torch.uint8)
-        d_tab = self._grow(slot, "d_tab", tb.nbytes, torch.uint8)
+        d_src = grow(slot, "d_src", blob.nbytes + 16, torch.uint8, self.device)
+        d_tab = grow(slot, "d_tab", tb.nbytes, torch.uint8, self.device)
         raw_bytes = n * cr * cc * es
-        d_raw = self._grow(slot, "d_raw", raw_bytes, torch.uint8)
-        d_st = self._grow(slot, "d_status", n, torch.int32)
+        d_raw = grow(slot, "d_raw", raw_bytes, torch.uint8, self.device)
+        d_st = grow(slot, "d_status", n, torch.int32, self.device)
         raw_max = int(table["raw_len"].max()) if n else 0
         scr_bytes = int(L.tmh_inflate_scratch_bytes(n, raw_max))
-        d_scr = self._grow(slot, "d_scratch", max(scr_bytes, 4), torch.uint8)
+        d_scr = grow(slot, "d_scratch", max(scr_bytes, 4), torch.uint8, self.device)
         prev = slot.get("inflated")  # the slot's device buffers are free once its last block inflated
         with torch.cuda.stream(self.copy_stream):
             if prev is not None:
@@ -135,7 +138,7 @@ class DeviceChunkDecoder(object):
         inflated = torch.cuda.Event()
         inflated.record(self.stream)
         slot["inflated"] = inflated
-        h_st = self._grow(slot, "h_status", n, torch.int32, pinned=True)
+        h_st = grow(slot, "h_status", n, torch.int32)
         with torch.cuda.stream(self.stream):
             h_st[:n].copy_(d_st[:n], non_blocking=True)
             ev = torch.cuda.Event()

@@ -20,6 +20,7 @@ import ctypes as C
 import numpy as np
 
 from tmlibrary_amd import hip
+from tmlibrary_amd.models.device_decode import grow
 from tmlibrary_amd.models.file import h5py_chunk_shape, write_raw_chunks
 
 
@@ -39,18 +40,6 @@ class DeviceChunkEncoder(object):
         self.stream = stream if stream is not None else torch.cuda.Stream(self.device)
         self.slots = [dict() for _ in range(max(1, slots))]
         self.k = 0
-
-    def _grow(self, slot, name, n, dtype, pinned=False):
-        torch = self.torch
-        t = slot.get(name)
-        if t is None or t.numel() < n:
-            n = max(int(n * 1.25), 1)
-            if pinned:
-                t = torch.empty(n, dtype=dtype, pin_memory=True)
-            else:
-                t = torch.empty(n, dtype=dtype, device=self.device)
-            slot[name] = t
-        return t
 
     def deflate(self, sites, chunks=None):
         """``sites``: a device tensor or a numpy array, [n, H, W] (or [H, W])
@@ -94,12 +83,12 @@ class DeviceChunkEncoder(object):
             dst_bytes = n * int(L.tmh_deflate_bound(raw_max))
             scr_bytes = int(L.tmh_deflate_scratch_bytes(n, raw_max))
             esz = hip.ZCHUNK_DTYPE.itemsize
-            d_tab = self._grow(slot, "d_tab", n * esz, torch.uint8)
-            d_raw = self._grow(slot, "d_raw", raw_bytes, torch.uint8)
-            d_dst = self._grow(slot, "d_dst", dst_bytes, torch.uint8)
-            d_scr = self._grow(slot, "d_scratch", max(scr_bytes, 16), torch.uint8)
-            d_st = self._grow(slot, "d_status", n, torch.int32)
-            d_tot = self._grow(slot, "d_total", 1, torch.int64)
+            d_tab = grow(slot, "d_tab", n * esz, torch.uint8, self.device)
+            d_raw = grow(slot, "d_raw", raw_bytes, torch.uint8, self.device)
+            d_dst = grow(slot, "d_dst", dst_bytes, torch.uint8, self.device)
+            d_scr = grow(slot, "d_scratch", max(scr_bytes, 16), torch.uint8, self.device)
+            d_st = grow(slot, "d_status", n, torch.int32, self.device)
+            d_tot = grow(slot, "d_total", 1, torch.int64, self.device)
             sp = C.c_void_p(self.stream.cuda_stream)
             hip.check(L.tmh_gather_chunks_device(C.c_void_p(dev.data_ptr()), n_img, H, W, es, cr, cc,
                                                  C.c_void_p(d_tab.data_ptr()),
@@ -110,9 +99,9 @@ class DeviceChunkEncoder(object):
                                            C.c_void_p(d_scr.data_ptr()), d_scr.numel(),
                                            C.c_void_p(d_st.data_ptr()),
                                            C.c_void_p(d_tot.data_ptr()), sp))
-            h_tab = self._grow(slot, "h_tab", n * esz, torch.uint8, pinned=True)
-            h_st = self._grow(slot, "h_status", n, torch.int32, pinned=True)
-            h_tot = self._grow(slot, "h_total", 1, torch.int64, pinned=True)
+            h_tab = grow(slot, "h_tab", n * esz, torch.uint8)
+            h_st = grow(slot, "h_status", n, torch.int32)
+            h_tot = grow(slot, "h_total", 1, torch.int64)
             h_tab[:n * esz].copy_(d_tab[:n * esz], non_blocking=True)
             h_st[:n].copy_(d_st[:n], non_blocking=True)
             h_tot.copy_(d_tot[:1], non_blocking=True)
@@ -124,7 +113,7 @@ class DeviceChunkEncoder(object):
                 raise IOError("chunk %d: %s (%d of %d chunks failed to deflate)"
                               % (int(bad[0]), hip.Z_STATUS.get(int(st[bad[0]]), "error"),
                                  bad.size, n))
-            h_blob = self._grow(slot, "h_blob", total, torch.uint8, pinned=True)
+            h_blob = grow(slot, "h_blob", total, torch.uint8)
             h_blob[:total].copy_(d_dst[:total], non_blocking=True)
             self.stream.synchronize()
         table = h_tab[:n * esz].numpy().view(hip.ZCHUNK_DTYPE)

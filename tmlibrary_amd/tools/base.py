@@ -68,22 +68,17 @@ class DeviceTable(object):
         self.X = X
         self.n, self.d = X.shape
         self.scaler = scaler
-        self._ptrs = []
+        self._buffers = []
         self.x = self.center = self.scale = None
 
     def _upload(self, a):
-        L = hip.lib()
-        p = C.c_void_p()
-        hip.check(L.tmh_malloc_device(C.byref(p), a.nbytes))
-        self._ptrs.append(p)
-        hip.check(L.tmh_memcpy(p, hip.ptr(a), a.nbytes, 0, None))
-        return p
+        self._buffers.append(hip.DeviceBuffer.from_array(a))
+        return self._buffers[-1]
 
     def alloc(self, nbytes):
-        p = C.c_void_p()
-        hip.check(hip.lib().tmh_malloc_device(C.byref(p), nbytes))
-        self._ptrs.append(p)
-        return p
+        """A ``hip.DeviceBuffer`` that lives as long as the table."""
+        self._buffers.append(hip.DeviceBuffer(nbytes))
+        return self._buffers[-1]
 
     def __enter__(self):
         try:
@@ -97,10 +92,9 @@ class DeviceTable(object):
         return self
 
     def __exit__(self, *exc):
-        L = hip.lib()
-        for p in self._ptrs:
-            L.tmh_free_device(p)
-        self._ptrs = []
+        for buf in self._buffers:
+            buf.free()
+        self._buffers = []
         return False
 
 
@@ -288,8 +282,7 @@ class KMeans(object):
                     float(self.tol), hip.ptr(centres), dev_labels, C.byref(inertia),
                     C.byref(n_iter), C.byref(tol_abs), None))
                 if best is None or inertia.value < best[0]:
-                    labels = np.empty(n, dtype=np.int32)
-                    hip.check(L.tmh_memcpy(hip.ptr(labels), dev_labels, labels.nbytes, 1, None))
+                    labels = dev_labels.get(n, np.int32)
                     hip.check(L.tmh_synchronize(None))
                     best = (inertia.value, centres, labels, n_iter.value, tol_abs.value)
                 if init is not None:

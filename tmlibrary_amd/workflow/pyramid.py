@@ -30,6 +30,7 @@ numpy and needs no device.
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes as C
 import itertools
 
@@ -530,15 +531,13 @@ class Pyramid(object):
         self.dimensions = list(geometry.dimensions)
         self.empty_base_tiles = geometry.get_empty_base_tile_coordinates()
         self._closed = False
-        self._levels = [None] * self.depth     # device pointers
+        self._levels = [None] * self.depth     # hip.DeviceBuffer
         self._last = [None] * self.depth       # (height, width) of the last tile row / column
 
     def _alloc(self, z):
         rows, cols = self.dimensions[z]
-        p = C.c_void_p()
-        hip.check(hip.lib().tmh_malloc_device(C.byref(p), rows * cols * TILE_SIZE * TILE_SIZE))
-        self._levels[z] = p
-        return p
+        self._levels[z] = hip.DeviceBuffer(rows * cols * TILE_SIZE * TILE_SIZE)
+        return self._levels[z]
 
     def _check(self, z, y=0, x=0):
         if self._closed:
@@ -558,10 +557,8 @@ class Pyramid(object):
                 self._last[z][1] if x == cols - 1 else TILE_SIZE)
 
     def _read_tiles(self, z, first, count):
-        buf = np.empty((count, TILE_SIZE, TILE_SIZE), dtype=np.uint8)
-        src = C.c_void_p(self._levels[z].value + first * TILE_SIZE * TILE_SIZE)
-        hip.check(hip.lib().tmh_memcpy(hip.ptr(buf), src, buf.nbytes, 1, None))
-        return buf
+        return self._levels[z].get((count, TILE_SIZE, TILE_SIZE), np.uint8,
+                                   first * TILE_SIZE * TILE_SIZE)
 
     def tile(self, z, y, x):
         """Tile (y, x) of level z as a ``PyramidTile`` of its ragged size."""
@@ -580,7 +577,7 @@ class Pyramid(object):
         """(device pointer, tile rows, tile columns, last row's height, last
         column's width) of level z's tile-major storage."""
         self._check(z)
-        return (self._levels[z],) + tuple(self.dimensions[z]) + tuple(self._last[z])
+        return (self._levels[z].ptr,) + tuple(self.dimensions[z]) + tuple(self._last[z])
 
     def _quality(self, quality):
         if quality is None:
@@ -598,14 +595,9 @@ class Pyramid(object):
         quality = self._quality(quality)
         L = hip.lib()
         rows, cols = self.dimensions[z]
-        out = C.c_void_p()
-        hip.check(L.tmh_malloc_device(C.byref(out), rows * cols * TILE_SIZE * TILE_SIZE))
-        try:
+        with hip.DeviceBuffer(rows * cols * TILE_SIZE * TILE_SIZE) as out:
             hip.check(L.tmh_jpeg_roundtrip_level_device(*self.device_level(z), quality, out, stream))
-            tiles = np.empty((rows, cols, TILE_SIZE, TILE_SIZE), dtype=np.uint8)
-            hip.check(L.tmh_memcpy(hip.ptr(tiles), out, tiles.nbytes, 1, stream))
-        finally:
-            L.tmh_free_device(out)
+            tiles = out.get((rows, cols, TILE_SIZE, TILE_SIZE), np.uint8, stream=stream)
         return tiles_to_array(tiles, self._last[z][0], self._last[z][1])
 
     def encode_level(self, z, quality=None, stream=None):
@@ -621,23 +613,15 @@ class Pyramid(object):
         L = hip.lib()
         level = self.device_level(z)
         n = level[1] * level[2]
-        d_off, d_out = C.c_void_p(), C.c_void_p()
         total = C.c_int64(0)
-        try:
-            hip.check(L.tmh_malloc_device(C.byref(d_off), (n + 1) * 8))
+        with hip.DeviceBuffer((n + 1) * 8) as d_off:
             hip.check(L.tmh_jpeg_encode_level_device(*level, int(quality), None, 0, d_off,
                                                      C.byref(total), stream))
-            hip.check(L.tmh_malloc_device(C.byref(d_out), total.value))
-            hip.check(L.tmh_jpeg_encode_level_device(*level, int(quality), d_out, total.value,
-                                                     d_off, C.byref(total), stream))
-            blob = np.empty(total.value, dtype=np.uint8)
-            offsets = np.empty(n + 1, dtype=np.int64)
-            hip.check(L.tmh_memcpy(hip.ptr(blob), d_out, blob.nbytes, 1, stream))
-            hip.check(L.tmh_memcpy(hip.ptr(offsets), d_off, offsets.nbytes, 1, stream))
-        finally:
-            for p in (d_off, d_out):
-                if p.value:
-                    L.tmh_free_device(p)
+            with hip.DeviceBuffer(total.value) as d_out:
+                hip.check(L.tmh_jpeg_encode_level_device(*level, int(quality), d_out, total.value,
+                                                         d_off, C.byref(total), stream))
+                blob = d_out.get(total.value, np.uint8, stream=stream)
+                offsets = d_off.get(n + 1, np.int64, stream=stream)
         return EncodedLevel(blob, offsets, self.dimensions[z])
 
     def iter_jpeg_tiles(self, quality=None):
@@ -656,9 +640,9 @@ class Pyramid(object):
     def close(self):
         self._closed = True
         levels, self._levels = self._levels, [None] * self.depth
-        for p in levels:
-            if p is not None:
-                hip.lib().tmh_free_device(p)
+        for buf in levels:
+            if buf is not None:
+                buf.free()
 
     def __enter__(self):
         return self
@@ -678,9 +662,7 @@ def _odd_mosaics_on_host(pyr, z, src=None):
     device pass left them unwritten; the exact area mean on the host.  ``src``:
     the device level the source tiles are read from (default: level z + 1
     itself; the stored pyramid passes its JPEG round trip)."""
-    L = hip.lib()
     rows, cols = pyr.dimensions[z]
-    src_rows, src_cols = pyr.dimensions[z + 1]
     for y, x in itertools.product(range(rows), range(cols)):
         coords = pyr.geometry.calc_coordinates_of_next_higher_level(z, y, x)
         pre_rows = sorted(set(c[0] for c in coords))
@@ -694,17 +676,15 @@ def _odd_mosaics_on_host(pyr, z, src=None):
         half = _area_mean_odd(mosaic)
         full = np.zeros((TILE_SIZE, TILE_SIZE), dtype=np.uint8)
         full[:half.shape[0], :half.shape[1]] = half
-        dst = C.c_void_p(pyr._levels[z].value + (y * cols + x) * TILE_SIZE * TILE_SIZE)
-        hip.check(L.tmh_memcpy(dst, hip.ptr(full), full.nbytes, 0, None))
+        pyr._levels[z].put(full, (y * cols + x) * TILE_SIZE * TILE_SIZE)
 
 
 def _source_tile(pyr, z, y, x, src):
     if src is None:
         return pyr.tile(z, y, x).array
     h, w = pyr.tile_dimensions(z, y, x)
-    full = np.empty((TILE_SIZE, TILE_SIZE), dtype=np.uint8)
-    at = C.c_void_p(src.value + (y * pyr.dimensions[z][1] + x) * TILE_SIZE * TILE_SIZE)
-    hip.check(hip.lib().tmh_memcpy(hip.ptr(full), at, full.nbytes, 1, None))
+    full = src.get((TILE_SIZE, TILE_SIZE), np.uint8,
+                   (y * pyr.dimensions[z][1] + x) * TILE_SIZE * TILE_SIZE)
     return np.ascontiguousarray(full[:h, :w])
 
 
@@ -733,26 +713,26 @@ def build_pyramid(geometry, sites_u8, table=None, stream=None, jpeg_quality=None
     table = np.ascontiguousarray(table, dtype=hip.TILE_RECT_DTYPE)
     n, (H, W) = len(geometry.sites), geometry.image_size
     dev = _device_pointer(sites_u8)
-    staged = None
     if dev is None:
         a = np.ascontiguousarray(sites_u8)
         if a.dtype != np.uint8 or a.shape != (n, H, W):
             raise ValueError("sites_u8 must be a uint8 array of shape %r" % ((n, H, W),))
-        staged = C.c_void_p()
-        hip.check(L.tmh_malloc_device(C.byref(staged), a.nbytes))
-        dev = staged.value
     pyr = Pyramid(geometry, jpeg_quality)
-    scratch = C.c_void_p()
+    scratch = None
+    temporaries = contextlib.ExitStack()    # the staged sites and the round trip's scratch
     try:
-        if staged is not None:
-            hip.check(L.tmh_memcpy(staged, hip.ptr(a), a.nbytes, 0, stream))
+        if dev is None:
+            staged = temporaries.enter_context(hip.DeviceBuffer(a.nbytes))
+            staged.put(a, stream=stream)
+            dev = staged.ptr.value
         z = pyr.depth - 1
         rows, cols = pyr.dimensions[z]
         hip.check(L.tmh_tiles_base_device(C.c_void_p(dev), n, H, W, hip.ptr(table), len(table),
                                           pyr._alloc(z), rows, cols, stream))
         pyr._last[z] = (TILE_SIZE, TILE_SIZE)
         if jpeg_quality is not None and z > 0:
-            hip.check(L.tmh_malloc_device(C.byref(scratch), rows * cols * TILE_SIZE * TILE_SIZE))
+            scratch = temporaries.enter_context(
+                hip.DeviceBuffer(rows * cols * TILE_SIZE * TILE_SIZE))
         while z > 0:
             rows, cols = pyr.dimensions[z]
             if pyr.dimensions[z - 1] != ((rows + 1) // 2, (cols + 1) // 2):
@@ -771,15 +751,12 @@ def build_pyramid(geometry, sites_u8, table=None, stream=None, jpeg_quality=None
             pyr._last[z - 1] = (lh.value, lw.value)
             if pyr._last[z][0] % 2 or pyr._last[z][1] % 2:
                 hip.check(L.tmh_synchronize(stream))
-                _odd_mosaics_on_host(pyr, z - 1, None if jpeg_quality is None else scratch)
+                _odd_mosaics_on_host(pyr, z - 1, scratch)
             z -= 1
         hip.check(L.tmh_synchronize(stream))
     except Exception:
         pyr.close()
         raise
     finally:
-        if staged is not None:
-            L.tmh_free_device(staged)
-        if scratch.value:
-            L.tmh_free_device(scratch)
+        temporaries.close()
     return pyr

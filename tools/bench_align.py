@@ -30,7 +30,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bench_pyramid import dmalloc, kernel_ms  # noqa: E402
+from bench_pyramid import kernel_ms  # noqa: E402
 from tmlibrary_amd import hip  # noqa: E402
 from tmlibrary_amd.models.file import granted_cores  # noqa: E402
 
@@ -152,17 +152,15 @@ def main():
 
     # the box's flat copy: read 2 B/px and write them, 256 MiB each way
     npx, probe_sites = 1 << 20, 128
-    d_a, d_b = dmalloc(L, probe_sites * npx * 2), dmalloc(L, probe_sites * npx * 2)
-    ptrs = np.array([d_a.value, d_b.value], dtype=np.uint64)
-    d_ptrs = dmalloc(L, 16)
-    hip.check(L.tmh_memcpy(d_ptrs, hip.ptr(ptrs), 16, 0, None))
     copy_ms = C.c_double()
-    for reps in (a.warmup, a.reps):
-        hip.check(L.tmh_box_probe_device(d_ptrs, C.c_void_p(d_ptrs.value + 8), 24, probe_sites,
-                                         1024, 1024, 2, reps, None, C.byref(copy_ms), None))
+    with hip.DeviceBuffer(probe_sites * npx * 2) as d_a, \
+            hip.DeviceBuffer(probe_sites * npx * 2) as d_b:
+        ptrs = np.array([d_a.ptr.value, d_b.ptr.value], dtype=np.uint64)
+        with hip.DeviceBuffer.from_array(ptrs) as d_ptrs:
+            for reps in (a.warmup, a.reps):
+                hip.check(L.tmh_box_probe_device(d_ptrs, d_ptrs.at(8), 24, probe_sites, 1024, 1024,
+                                                 2, reps, None, C.byref(copy_ms), None))
     copy_gbs = 2 * probe_sites * npx * 2 / (copy_ms.value * 1e6)  # bytes read + written
-    for p in (d_a, d_b, d_ptrs):
-        L.tmh_free_device(p)
 
     doc = {"tool": "bench_align", "flat_copy_gb_per_s": round(copy_gbs, 1), "threads": threads,
            "shapes": []}

@@ -85,7 +85,6 @@ def bench_shape(L, n, d, a, read_gbs):
     with DeviceTable(X, scaler) as t:
         dev_labels = t.alloc(4 * n)
         dev_values = t.alloc(8 * n * max(CLASSES, pairs))
-        f_labels, s_labels = np.empty(n, np.int32), np.empty(n, np.int32)
 
         def forest_predict(proba=False):
             hip.check(L.tmh_forest_predict_device(forest.handle(), t.x, n, dev_labels,
@@ -103,7 +102,7 @@ def bench_shape(L, n, d, a, read_gbs):
         fo["with_proba"] = timed(L, lambda: forest_predict(True),
                                  "forest_predict_" + ("lds" if route == "lds" else "mem"), a, flat_ms)
         forest_predict()
-        hip.check(L.tmh_memcpy(hip.ptr(f_labels), dev_labels, f_labels.nbytes, 1, None))
+        f_labels = dev_labels.get(n, np.int32)
         hip.check(L.tmh_synchronize(None))
         if route == "lds":
             forest.memory_route = True
@@ -115,7 +114,7 @@ def bench_shape(L, n, d, a, read_gbs):
         so = {"support_vectors": int(svm.sv.shape[0]), "gamma": svm.gamma, "tile": tile,
               "tiles": tiles, "one_route": timed(L, svc_predict, "svc_predict", a, flat_ms)}
         svc_predict()
-        hip.check(L.tmh_memcpy(hip.ptr(s_labels), dev_labels, s_labels.nbytes, 1, None))
+        s_labels = dev_labels.get(n, np.int32)
         hip.check(L.tmh_synchronize(None))
         svm.tile_cap = 8
         so["streamed_tile"], so["streamed_tiles"] = svm.tile()

@@ -160,8 +160,7 @@ def bench_shape(L, n, d, k, a, read_gbs):
         # the closing assign (no sums) is counted in when the labels still moved
         per_iter = (as_ev + up_ev) / short
         fit()
-        labels = np.empty(n, np.int32)
-        hip.check(L.tmh_memcpy(hip.ptr(labels), dev_labels, labels.nbytes, 1, None))
+        labels = dev_labels.get(n, np.int32)
         hip.check(L.tmh_synchronize(None))
         dev_inertia = inertia.value
 

@@ -32,7 +32,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bench_pyramid import T, dmalloc, kernel_ms, layer  # noqa: E402
+from bench_pyramid import T, kernel_ms, layer, resident_sites  # noqa: E402
 from tmlibrary_amd import hip  # noqa: E402
 from tmlibrary_amd.workflow.pyramid import plan_base_tiles  # noqa: E402
 
@@ -93,22 +93,16 @@ def main():
     table = plan_base_tiles(g)
     rows, cols = g.dimensions[-1]
     site = site_image(a.content, H, W)
-    d_sites = dmalloc(L, n * H * W)
-    hip.check(L.tmh_memcpy(d_sites, hip.ptr(site), site.nbytes, 0, None))
-    have = 1
-    while have < n:      # doubling device-to-device copies
-        k = min(have, n - have)
-        hip.check(L.tmh_memcpy(C.c_void_p(d_sites.value + have * H * W), d_sites, k * H * W, 2, None))
-        have += k
+    d_sites = resident_sites(site, n)
 
     levels = [(rows, cols)]
     while levels[-1] != (1, 1):
         levels.append(((levels[-1][0] + 1) // 2, (levels[-1][1] + 1) // 2))
-    d_levels = [dmalloc(L, r * c * T * T) for r, c in levels]
+    d_levels = [hip.DeviceBuffer(r * c * T * T) for r, c in levels]
     lasts = [(T, T)]
     hip.check(L.tmh_tiles_base_device(d_sites, n, H, W, hip.ptr(table), len(table), d_levels[0],
                                       rows, cols, None))
-    L.tmh_free_device(d_sites)
+    d_sites.free()
     for z in range(len(levels) - 1):
         lh, lw = C.c_int(), C.c_int()
         hip.check(L.tmh_pyramid_shrink2_device(d_levels[z], levels[z][0], levels[z][1], lasts[z][0],
@@ -123,27 +117,24 @@ def main():
     level_b = rows * cols * T * T
     npx = 1 << 20
     probe_sites = level_b // (2 * npx)
-    d_probe_out = dmalloc(L, probe_sites * 2 * npx)
-    ptrs = np.array([d_levels[0].value, d_probe_out.value], dtype=np.uint64)
-    d_ptrs = dmalloc(L, 16)
-    hip.check(L.tmh_memcpy(d_ptrs, hip.ptr(ptrs), 16, 0, None))
     copy_ms = C.c_double()
-    for reps in (a.warmup, a.reps):
-        hip.check(L.tmh_box_probe_device(d_ptrs, C.c_void_p(d_ptrs.value + 8), 24, probe_sites,
-                                         1024, 1024, 2, reps, None, C.byref(copy_ms), None))
+    with hip.DeviceBuffer(probe_sites * 2 * npx) as d_probe_out:
+        ptrs = np.array([d_levels[0].ptr.value, d_probe_out.ptr.value], dtype=np.uint64)
+        with hip.DeviceBuffer.from_array(ptrs) as d_ptrs:
+            for reps in (a.warmup, a.reps):
+                hip.check(L.tmh_box_probe_device(d_ptrs, d_ptrs.at(8), 24, probe_sites, 1024, 1024,
+                                                 2, reps, None, C.byref(copy_ms), None))
     copy_ms = copy_ms.value * level_b / (probe_sites * 2 * npx)
-    for p in (d_probe_out, d_ptrs):
-        L.tmh_free_device(p)
 
     hip.check(L.tmh_profile_enable(1))
     per_level = []
     for z, (r, c) in enumerate(levels):
         nt = r * c
-        d_off = dmalloc(L, (nt + 1) * 8)
         total = C.c_int64()
+        d_off = hip.DeviceBuffer((nt + 1) * 8)
         hip.check(L.tmh_jpeg_encode_level_device(d_levels[z], r, c, lasts[z][0], lasts[z][1],
                                                  a.quality, None, 0, d_off, C.byref(total), None))
-        d_out = dmalloc(L, total.value)
+        d_out = hip.DeviceBuffer(total.value)
         for rep in range(a.warmup + a.reps):
             if rep == a.warmup:
                 hip.check(L.tmh_profile_reset())
@@ -153,27 +144,23 @@ def main():
         m_ms, m_n = kernel_ms(L, "jpeg_measure")
         w_ms, w_n = kernel_ms(L, "jpeg_write")
         assert m_n == w_n == a.reps
-        offsets = np.empty(nt + 1, dtype=np.int64)
-        hip.check(L.tmh_memcpy(hip.ptr(offsets), d_off, offsets.nbytes, 1, None))
+        offsets = d_off.get(nt + 1, np.int64)
         m_ms, w_ms = m_ms / m_n, w_ms / w_n
         per_level.append({
             "tiles": [r, c], "last": list(lasts[z]), "measure_ms": round(m_ms, 4),
             "write_ms": round(w_ms, 4), "writing_call_ms": round(m_ms + w_ms, 4),
             "tiles_per_s": round(nt / (m_ms + w_ms) * 1e3, 1), "output_bytes": int(total.value),
             "files_of_1100_bytes": round(float(np.mean(np.diff(offsets) == 1100)), 4)})
-        for p in (d_off, d_out):
-            L.tmh_free_device(p)
+        d_off.free()
+        d_out.free()
     hip.check(L.tmh_profile_enable(0))
 
     pillow = None
     if a.pillow_tiles > 0:
         pick = np.sort(np.random.default_rng(1).choice(rows * cols, min(a.pillow_tiles, rows * cols),
                                                        replace=False))
-        tiles = np.empty((len(pick), T, T), dtype=np.uint8)
-        for i, t in enumerate(pick):
-            hip.check(L.tmh_memcpy(hip.ptr(tiles[i]), C.c_void_p(d_levels[0].value + int(t) * T * T),
-                                   T * T, 1, None))
-        pillow = pillow_rate(list(tiles), min(16, os.cpu_count() or 1), a.quality)
+        tiles = [d_levels[0].get((T, T), np.uint8, int(t) * T * T) for t in pick]
+        pillow = pillow_rate(tiles, min(16, os.cpu_count() or 1), a.quality)
 
     base = per_level[0]
     all_ms = sum(p["writing_call_ms"] for p in per_level)
@@ -194,8 +181,6 @@ def main():
         "levels": per_level,
         "pillow": pillow,
     }
-    for p in d_levels:
-        L.tmh_free_device(p)
     line = json.dumps(result)
     print(line)
     if a.out:

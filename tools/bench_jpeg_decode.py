@@ -33,7 +33,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench_jpeg import site_image  # noqa: E402
-from bench_pyramid import T, dmalloc, kernel_ms, layer  # noqa: E402
+from bench_pyramid import T, kernel_ms, layer, resident_sites  # noqa: E402
 from tmlibrary_amd import hip  # noqa: E402
 from tmlibrary_amd.workflow.pyramid import plan_base_tiles  # noqa: E402
 
@@ -79,23 +79,17 @@ def main():
     table = plan_base_tiles(g)
     rows, cols = g.dimensions[-1]
     site = site_image(a.content, H, W)
-    d_sites = dmalloc(L, n * H * W)
-    hip.check(L.tmh_memcpy(d_sites, hip.ptr(site), site.nbytes, 0, None))
-    have = 1
-    while have < n:      # doubling device-to-device copies
-        k = min(have, n - have)
-        hip.check(L.tmh_memcpy(C.c_void_p(d_sites.value + have * H * W), d_sites, k * H * W, 2, None))
-        have += k
+    d_sites = resident_sites(site, n)
 
     levels = [(rows, cols)]
     while levels[-1] != (1, 1):
         levels.append(((levels[-1][0] + 1) // 2, (levels[-1][1] + 1) // 2))
-    d_levels = [dmalloc(L, r * c * T * T) for r, c in levels]
+    d_levels = [hip.DeviceBuffer(r * c * T * T) for r, c in levels]
     level_b = rows * cols * T * T
-    d_scratch = dmalloc(L, level_b)
+    d_scratch = hip.DeviceBuffer(level_b)
     hip.check(L.tmh_tiles_base_device(d_sites, n, H, W, hip.ptr(table), len(table), d_levels[0],
                                       rows, cols, None))
-    L.tmh_free_device(d_sites)
+    d_sites.free()
 
     def lower_levels(quality):
         """levels 1.. from the base, as build_pyramid queues them (a mosaic
@@ -120,15 +114,13 @@ def main():
     # the box's flat copy of the base level's bytes (read them once, write them once)
     npx = 1 << 20
     probe_sites = level_b // (2 * npx)
-    ptrs = np.array([d_levels[0].value, d_scratch.value], dtype=np.uint64)
-    d_ptrs = dmalloc(L, 16)
-    hip.check(L.tmh_memcpy(d_ptrs, hip.ptr(ptrs), 16, 0, None))
+    ptrs = np.array([d_levels[0].ptr.value, d_scratch.ptr.value], dtype=np.uint64)
     copy_ms = C.c_double()
-    for reps in (a.warmup, a.reps):
-        hip.check(L.tmh_box_probe_device(d_ptrs, C.c_void_p(d_ptrs.value + 8), 24, probe_sites,
-                                         1024, 1024, 2, reps, None, C.byref(copy_ms), None))
+    with hip.DeviceBuffer.from_array(ptrs) as d_ptrs:
+        for reps in (a.warmup, a.reps):
+            hip.check(L.tmh_box_probe_device(d_ptrs, d_ptrs.at(8), 24, probe_sites, 1024, 1024, 2,
+                                             reps, None, C.byref(copy_ms), None))
     copy_ms = copy_ms.value * level_b / (probe_sites * 2 * npx)
-    L.tmh_free_device(d_ptrs)
 
     hip.check(L.tmh_profile_enable(1))
 
@@ -154,7 +146,7 @@ def main():
     decode_levels, base_files, measure_ms = [], None, None
     for z, (r, c) in enumerate(levels):
         nt = r * c
-        d_off = dmalloc(L, (nt + 1) * 8)
+        d_off = hip.DeviceBuffer((nt + 1) * 8)
         total = C.c_int64()
         args = (d_levels[z], r, c, lasts[z][0], lasts[z][1], a.quality)
         if z == 0:
@@ -162,32 +154,25 @@ def main():
                 *args, None, 0, d_off, C.byref(total), None)))
             measure_ms = m["jpeg_measure"]
         hip.check(L.tmh_jpeg_encode_level_device(*args, None, 0, d_off, C.byref(total), None))
-        d_blob = dmalloc(L, total.value)
+        d_blob = hip.DeviceBuffer(total.value)
         hip.check(L.tmh_jpeg_encode_level_device(*args, d_blob, total.value, d_off, C.byref(total),
                                                  None))
-        d_dims, d_status = dmalloc(L, nt * 8), dmalloc(L, nt * 4)
+        d_dims, d_status = hip.DeviceBuffer(nt * 8), hip.DeviceBuffer(nt * 4)
         # decoded into the scratch level: the base level's size at the most
         ms, _ = timed(["jpeg_decode_tiles"], lambda: hip.check(L.tmh_jpeg_decode_tiles_device(
             d_blob, d_off, nt, d_scratch, d_dims, d_status, None)))
-        status = np.empty(nt, dtype=np.int32)
-        hip.check(L.tmh_memcpy(hip.ptr(status), d_status, status.nbytes, 1, None))
-        assert not status.any(), "a file of level %d was not decoded" % z
+        assert not d_status.get(nt, np.int32).any(), "a file of level %d was not decoded" % z
         decode_levels.append({"tiles": [r, c], "last": list(lasts[z]),
                               "decode_ms": round(ms["jpeg_decode_tiles"], 4),
                               "tiles_per_s": round(nt / ms["jpeg_decode_tiles"] * 1e3, 1),
                               "input_bytes": int(total.value)})
         if z == 0 and a.pillow_tiles > 0:
-            offsets = np.empty(nt + 1, dtype=np.int64)
-            hip.check(L.tmh_memcpy(hip.ptr(offsets), d_off, offsets.nbytes, 1, None))
+            offsets = d_off.get(nt + 1, np.int64)
             pick = np.sort(np.random.default_rng(1).choice(nt, min(a.pillow_tiles, nt), replace=False))
-            base_files = []
-            for t in pick:
-                buf = np.empty(int(offsets[t + 1] - offsets[t]), dtype=np.uint8)
-                hip.check(L.tmh_memcpy(hip.ptr(buf), C.c_void_p(d_blob.value + int(offsets[t])),
-                                       buf.nbytes, 1, None))
-                base_files.append(buf.tobytes())
-        for p in (d_off, d_blob, d_dims, d_status):
-            L.tmh_free_device(p)
+            base_files = [d_blob.get(int(offsets[t + 1] - offsets[t]), np.uint8,
+                                     int(offsets[t])).tobytes() for t in pick]
+        for buf in (d_off, d_blob, d_dims, d_status):
+            buf.free()
     hip.check(L.tmh_profile_enable(0))
 
     pillow = pillow_rate(base_files, min(16, os.cpu_count() or 1)) if base_files else None
@@ -217,8 +202,6 @@ def main():
         "decode_levels": decode_levels,
         "pillow_decode": pillow,
     }
-    for p in d_levels + [d_scratch]:
-        L.tmh_free_device(p)
     line = json.dumps(result)
     print(line)
     if a.out:

@@ -31,7 +31,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bench_pyramid import dmalloc, kernel_ms  # noqa: E402
+from bench_pyramid import kernel_ms  # noqa: E402
 from tmlibrary_amd import hip  # noqa: E402
 from tmlibrary_amd.image import Corrector, align_window  # noqa: E402
 from tmlibrary_amd.models.file import granted_cores  # noqa: E402
@@ -42,19 +42,17 @@ H, W = 2160, 2560
 def box_rates(L, warmup, reps):
     """(copy GB/s counting bytes read + written, read GB/s) of the flat probe."""
     npx, probe_sites = 1 << 20, 128
-    d_a, d_b = dmalloc(L, probe_sites * npx * 2), dmalloc(L, probe_sites * npx * 2)
-    ptrs = np.array([d_a.value, d_b.value], dtype=np.uint64)
-    d_ptrs = dmalloc(L, 16)
-    hip.check(L.tmh_memcpy(d_ptrs, hip.ptr(ptrs), 16, 0, None))
     out = []
-    for mode, factor in ((2, 2), (3, 1)):
-        ms = C.c_double()
-        for n in (warmup, reps):
-            hip.check(L.tmh_box_probe_device(d_ptrs, C.c_void_p(d_ptrs.value + 8), 24, probe_sites,
-                                             1024, 1024, mode, n, None, C.byref(ms), None))
-        out.append(factor * probe_sites * npx * 2 / (ms.value * 1e6))
-    for p in (d_a, d_b, d_ptrs):
-        L.tmh_free_device(p)
+    with hip.DeviceBuffer(probe_sites * npx * 2) as d_a, \
+            hip.DeviceBuffer(probe_sites * npx * 2) as d_b:
+        ptrs = np.array([d_a.ptr.value, d_b.ptr.value], dtype=np.uint64)
+        with hip.DeviceBuffer.from_array(ptrs) as d_ptrs:
+            for mode, factor in ((2, 2), (3, 1)):
+                ms = C.c_double()
+                for n in (warmup, reps):
+                    hip.check(L.tmh_box_probe_device(d_ptrs, d_ptrs.at(8), 24, probe_sites, 1024,
+                                                     1024, mode, n, None, C.byref(ms), None))
+                out.append(factor * probe_sites * npx * 2 / (ms.value * 1e6))
     return out
 
 

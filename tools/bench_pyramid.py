@@ -44,10 +44,12 @@ def layer(well_rows, well_cols, sites_per_side, size, spacer):
     return LayerGeometry(size, sites, dims)
 
 
-def dmalloc(L, nbytes):
-    p = C.c_void_p()
-    hip.check(L.tmh_malloc_device(C.byref(p), nbytes))
-    return p
+def resident_sites(site, n):
+    """n copies of one host site, back to back in a ``hip.DeviceBuffer``."""
+    d_sites = hip.DeviceBuffer(n * site.nbytes)
+    for i in range(n):
+        d_sites.put(site, i * site.nbytes)
+    return d_sites
 
 
 def kernel_ms(L, name):
@@ -79,37 +81,30 @@ def main():
     read_b = int((table["height"].astype(np.int64) * table["width"]).sum())
     write_b = rows * cols * T * T
 
-    # resident sites: one random site uploaded, replicated on the device
+    # resident sites: one random site, uploaded n times
     site = np.random.default_rng(0).integers(0, 256, (H, W), dtype=np.uint8)
-    d_sites = dmalloc(L, n * H * W)
-    hip.check(L.tmh_memcpy(d_sites, hip.ptr(site), site.nbytes, 0, None))
-    have = 1
-    while have < n:      # doubling device-to-device copies
-        k = min(have, n - have)
-        hip.check(L.tmh_memcpy(C.c_void_p(d_sites.value + have * H * W), d_sites, k * H * W, 2, None))
-        have += k
+    d_sites = resident_sites(site, n)
 
     levels = [(rows, cols)]
     while levels[-1] != (1, 1):
         levels.append(((levels[-1][0] + 1) // 2, (levels[-1][1] + 1) // 2))
-    d_levels = [dmalloc(L, r * c * T * T) for r, c in levels]
+    d_levels = [hip.DeviceBuffer(r * c * T * T) for r, c in levels]
 
     # the box's flat copy of the base pass's byte count: (read + write) / 2 each way
     npx = 1 << 20
     probe_sites = max(1, (read_b + write_b) // 2 // (2 * npx))
     assert probe_sites * 2 * npx <= write_b
-    d_probe_out = dmalloc(L, probe_sites * 2 * npx)
-    ptrs = np.array([d_levels[0].value, d_probe_out.value], dtype=np.uint64)
-    d_ptrs = dmalloc(L, 16)
-    hip.check(L.tmh_memcpy(d_ptrs, hip.ptr(ptrs), 16, 0, None))
+    d_probe_out = hip.DeviceBuffer(probe_sites * 2 * npx)
+    ptrs = np.array([d_levels[0].ptr.value, d_probe_out.ptr.value], dtype=np.uint64)
+    d_ptrs = hip.DeviceBuffer.from_array(ptrs)
     copy_ms = C.c_double()
-    hip.check(L.tmh_box_probe_device(d_ptrs, C.c_void_p(d_ptrs.value + 8), 24, probe_sites, 1024,
+    hip.check(L.tmh_box_probe_device(d_ptrs, d_ptrs.at(8), 24, probe_sites, 1024,
                                      1024, 2, a.warmup, None, C.byref(copy_ms), None))
-    hip.check(L.tmh_box_probe_device(d_ptrs, C.c_void_p(d_ptrs.value + 8), 24, probe_sites, 1024,
+    hip.check(L.tmh_box_probe_device(d_ptrs, d_ptrs.at(8), 24, probe_sites, 1024,
                                      1024, 2, a.reps, None, C.byref(copy_ms), None))
     copy_bytes = probe_sites * 2 * npx * 2
     copy_gbs = copy_bytes / copy_ms.value / 1e6
-    L.tmh_free_device(d_probe_out)
+    d_probe_out.free()
 
     hip.check(L.tmh_profile_enable(1))
     for rep in range(a.warmup + a.reps):
@@ -156,8 +151,6 @@ def main():
         "shrink_total_ms": round(sum(s["ms"] for s in shrink), 4),
         "shrink_total_bytes": sum(s["bytes"] for s in shrink),
     }
-    for p in [d_sites, d_ptrs] + d_levels:
-        L.tmh_free_device(p)
     line = json.dumps(result)
     print(line)
     if a.out:
