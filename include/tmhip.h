@@ -754,6 +754,35 @@ int tmh_deflate_images(const void* host_images, int64_t n_images, int height, in
 int tmh_zproject_max(const void* host_planes, int64_t n_sites, int z, int height, int width,
                      int elem_bytes, void* host_out);
 
+/* ---- channel images as PNG files ------------------------------------------
+ * tmlib/image.py:672-682 (ChannelImage.png_encode): how a site leaves as a
+ * picture.  dev_images[n_images][height][width], elem_bytes 1 or 2, become
+ * n_images PNG files: greyscale (colour type 0), bit depth 8 or 16, no
+ * interlace, one filter per row chosen by the smallest sum of absolute
+ * filtered values, the zlib stream (CM 8, CINFO 7, as tmh_deflate_device
+ * writes) cut into pieces of tmh_png_piece_bytes() filtered bytes, one IDAT
+ * chunk per piece and one more for the Adler-32.  Any PNG reader decodes them
+ * to the input pixels; the bytes depend on the input alone
+ * (tests/png_host.cpp builds the same encoder for the CPU) but are not those
+ * of libpng.  File i is dev_dst[dev_offsets[i], dev_offsets[i + 1]), the files
+ * back to back; dev_offsets has n_images + 1 entries (device memory), the
+ * last one the total.  No file is longer than tmh_png_bound(height, width,
+ * elem_bytes); dst_bytes must be at least n_images times that.  dev_scratch:
+ * at least tmh_png_scratch_bytes(...) bytes, 16-byte aligned.  Images,
+ * destination, offsets and scratch must not overlap. */
+int64_t tmh_png_piece_bytes(void);
+int64_t tmh_png_bound(int height, int width, int elem_bytes);
+int64_t tmh_png_scratch_bytes(int64_t n_images, int height, int width, int elem_bytes);
+int tmh_png_encode_device(const void* dev_images, int64_t n_images, int height, int width,
+                          int elem_bytes, uint8_t* dev_dst, int64_t dst_bytes,
+                          int64_t* dev_offsets, void* dev_scratch, int64_t scratch_bytes,
+                          void* stream);
+/* Host-buffer form (unpipelined): host_offsets[n_images + 1] and the files in
+ * host_blob (*total bytes; TMH_EINVAL with *total set when blob_capacity is
+ * smaller). */
+int tmh_png_encode(const void* host_images, int64_t n_images, int height, int width, int elem_bytes,
+                   uint8_t* host_blob, int64_t blob_capacity, int64_t* host_offsets, int64_t* total);
+
 /* ---- jterator: a site's channel stacks and object tables -------------------
  * What jterator computes around its modules (which live in another package).
  *

@@ -570,6 +570,13 @@ void launch_deflate(const uint8_t* raw, int64_t raw_bytes, tmh_zchunk* chunks, i
                     int64_t* total, hipStream_t s);
 void launch_zproject_max(const void* planes, int64_t n_sites, int z, int height, int width,
                          int esize, void* out, hipStream_t s);
+// PNG files of greyscale images (png_kernels.hip): file i at dst + offsets[i],
+// offsets[n_images] their total
+int64_t png_piece_bytes();
+int64_t png_bound_bytes(int height, int width, int esize);
+int64_t png_scratch_bytes(int64_t n_images, int height, int width, int esize);
+void launch_png(const uint8_t* images, int64_t n_images, int height, int width, int esize,
+                uint8_t* dst, int64_t* offsets, uint8_t* scratch, hipStream_t s);
 // illuminati tile pyramid (pyramid_kernels.hip); d_tbeg[n_tiles + 1]: tile t's
 // rectangles are d_rects[d_tbeg[t], d_tbeg[t + 1])
 void launch_tiles_base(const uint8_t* sites, int64_t n_sites, int H, int W,

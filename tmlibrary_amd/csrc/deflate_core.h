@@ -597,7 +597,7 @@ TMH_DDEV void dzero_words(uint32_t* w, int64_t words, int tid, int nt) {
 // One chunk: src[0..raw_len) -> one RFC 1950 stream in the slot w (32-bit
 // words, deflate_slot_bytes(raw_len) at least); returns its bytes.  dist,
 // head: kDSeg uint16 and 1 << kDHashBits uint32 of scratch of this workgroup.
-TMH_DDEV int64_t deflate_chunk(DShared& z, const uint8_t* src, int64_t raw_len, uint32_t* w,
+[[maybe_unused]] TMH_DDEV int64_t deflate_chunk(DShared& z, const uint8_t* src, int64_t raw_len, uint32_t* w,
                                uint16_t* dist, uint32_t* head, int tid, int nt) {
   const int64_t slot_words = deflate_slot_bytes(raw_len) / 4;
   dzero_words(w, slot_words, tid, nt);
@@ -671,6 +671,107 @@ TMH_DDEV int64_t deflate_chunk(DShared& z, const uint8_t* src, int64_t raw_len, 
   for (int64_t i = tid; i < raw_len; i += nt) {
     const int64_t k = i / 65535;
     dput(w, 8 * (uint64_t)(2 + 5 * (k + 1) + i), src[i], 8);
+  }
+  TMH_DSYNC_GLOBAL();
+  return stored_len;
+}
+
+// Slot stride in bytes of a piece of at most raw_max bytes (deflate_piece): as
+// deflate_slot_bytes, with the sync block's 5 bytes in place of the Adler-32's 4.
+TMH_DHD int64_t deflate_piece_slot_bytes(int64_t raw_max) {
+  const int64_t nseg = raw_max > 0 ? (raw_max + kDSeg - 1) / kDSeg : 1;
+  return ((raw_max + 6 * nseg + 7 + 3) & ~int64_t(3)) + 8;
+}
+
+// the all-stored form of a piece: what deflate_piece never exceeds
+TMH_DHD int64_t deflate_piece_stored_bytes(int64_t raw_len, int first, int last) {
+  const int64_t nblk = raw_len > 0 ? (raw_len + 65534) / 65535 : 1;
+  return (first ? 2 : 0) + 5 * nblk + raw_len + (last ? 0 : 5);
+}
+
+// One piece of a zlib stream that several workgroups code side by side (PNG:
+// png_core.h): src[0..raw_len) coded exactly as deflate_chunk
+// codes its segments, but the zlib header only on the `first` piece, BFINAL
+// only on the last block of the `last` piece, and no Adler-32.  Every piece but
+// the last ends as zlib's Z_SYNC_FLUSH does, with an empty stored block (its
+// three header bits, the padding to a byte, 00 00 FF FF), so the pieces are
+// whole bytes and the stream is their concatenation.  sums[0], sums[1]: sum x
+// and sum (raw_len - i) x_i mod 65521, what the Adler-32 of the whole stream is
+// joined from.  A piece longer than its all-stored form is rewritten as that.
+// Returns the piece's bytes in the slot w of slot_words words.
+[[maybe_unused]] TMH_DDEV int64_t deflate_piece(DShared& z, const uint8_t* src, int64_t raw_len, int first, int last,
+                               uint32_t* w, int64_t slot_words, uint16_t* dist, uint32_t* head,
+                               uint32_t* sums, int tid, int nt) {
+  dzero_words(w, slot_words, tid, nt);
+  if (tid == 0) {
+    if (first) dput(w, 0, 0x78u | 0x5Eu << 8, 16);
+    z.bitpos = first ? 16 : 0;
+  }
+  const int64_t nseg = raw_len > 0 ? (raw_len + kDSeg - 1) / kDSeg : 1;
+  uint64_t sa = 0, sb = 0;
+  for (int64_t sg = 0; sg < nseg; ++sg) {
+    const int64_t s0 = sg * kDSeg;
+    const int n = (int)(raw_len - s0 < kDSeg ? raw_len - s0 : kDSeg);
+    TMH_DSYNC();
+    typedef uint32_t DV4 __attribute__((vector_size(16)));
+    const int nv = (reinterpret_cast<uintptr_t>(src + s0) & 15) == 0 ? n / 16 : 0;
+    for (int i = tid; i < nv; i += nt) {
+      const DV4 v = *reinterpret_cast<const DV4*>(src + s0 + 16 * (int64_t)i);
+      *reinterpret_cast<DV4*>(z.raw + 16 * i) = v;
+      uint32_t g0 = 0, g1 = 0;
+      for (int j = 0; j < 16; ++j) {
+        const uint32_t x = (v[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+        g0 += x;
+        g1 += (uint32_t)j * x;
+      }
+      sa += g0;
+      sb += (uint64_t)(raw_len - (s0 + 16 * (int64_t)i)) * g0 - g1;
+    }
+    for (int i = 16 * nv + tid; i < n + 16; i += nt) {
+      const uint8_t x = i < n ? src[s0 + i] : (uint8_t)0;
+      z.raw[i] = x;
+      sa += x;
+      sb += (uint64_t)(raw_len - (s0 + i)) * x;
+    }
+    TMH_DSYNC();
+    deflate_segment(z, n, last && sg == nseg - 1, w, dist, head, tid, nt);
+  }
+  z.red[0][tid] = sa % 65521u;
+  z.red[1][tid] = sb % 65521u;
+  TMH_DSYNC();
+  if (tid == 0) {
+    uint64_t ta = 0, tb = 0;
+    for (int t = 0; t < nt; ++t) ta += z.red[0][t], tb += z.red[1][t];
+    sums[0] = (uint32_t)(ta % 65521u);
+    sums[1] = (uint32_t)(tb % 65521u);
+    uint64_t pos = z.bitpos;
+    if (!last) {  // BFINAL 0, BTYPE 00 are zero bits of the zeroed slot; LEN 0
+      pos = (pos + 3 + 7) & ~uint64_t(7);
+      dput(w, pos + 16, 0xFFFFu, 16);
+      pos += 32;
+    }
+    z.bitpos = (pos + 7) & ~uint64_t(7);
+  }
+  TMH_DSYNC();
+  const int64_t stored_len = deflate_piece_stored_bytes(raw_len, first, last);
+  if ((int64_t)(z.bitpos >> 3) <= stored_len) return (int64_t)(z.bitpos >> 3);
+  const int64_t nblk = raw_len > 0 ? (raw_len + 65534) / 65535 : 1;
+  const int64_t h = first ? 2 : 0;
+  dzero_words(w, slot_words, tid, nt);
+  if (tid == 0) {
+    if (first) dput(w, 0, 0x78u | 0x5Eu << 8, 16);
+    for (int64_t k = 0; k < nblk; ++k) {
+      const uint64_t pos = 8 * (uint64_t)(h + 5 * k + 65535 * k);
+      const uint32_t len = (uint32_t)(raw_len - 65535 * k < 65535 ? raw_len - 65535 * k : 65535);
+      dput(w, pos, last && k == nblk - 1 ? 1u : 0u, 8);
+      dput(w, pos + 8, len, 16);
+      dput(w, pos + 24, len ^ 0xFFFFu, 16);
+    }
+    if (!last) dput(w, 8 * (uint64_t)(stored_len - 2), 0xFFFFu, 16);
+  }
+  for (int64_t i = tid; i < raw_len; i += nt) {
+    const int64_t k = i / 65535;
+    dput(w, 8 * (uint64_t)(h + 5 * (k + 1) + i), src[i], 8);
   }
   TMH_DSYNC_GLOBAL();
   return stored_len;

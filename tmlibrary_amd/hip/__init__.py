@@ -136,6 +136,11 @@ SIGNATURES = {
     "tmh_deflate_images": (_I, [_P, _I64, _I, _I, _I, _I, _I, _P, _P, _I64, _P,
                                 C.POINTER(_I64)]),
     "tmh_zproject_max": (_I, [_P, _I64, _I, _I, _I, _I, _P]),
+    "tmh_png_piece_bytes": (_I64, []),
+    "tmh_png_bound": (_I64, [_I, _I, _I]),
+    "tmh_png_scratch_bytes": (_I64, [_I64, _I, _I, _I]),
+    "tmh_png_encode_device": (_I, [_P, _I64, _I, _I, _I, _P, _I64, _P, _P, _I64, _P]),
+    "tmh_png_encode": (_I, [_P, _I64, _I, _I, _I, _P, _I64, _P, C.POINTER(_I64)]),
     "tmh_correct_stack_u16_device": (_I, [_P, _P, _P, _I64, _I, _I, _P, _P, _P, _I64, _I, _I, _I,
                                           _P]),
     "tmh_correct_stack_u16": (_I, [_P, _P, _P, _I64, _I, _I, _P, _P, _P, _I64, _I, _I, _I]),

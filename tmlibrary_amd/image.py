@@ -3,9 +3,9 @@
 Mirrors the hot-path subset of tmlib/image.py:
   ``Image``                (:35-454; array/metadata checks, ``smooth`` :287-311,
                             ``_shift_and_crop`` / ``align`` :345-454)
-  ``ChannelImage``         (:455-670; ``_map_to_uint8`` / ``scale`` :493-568,
+  ``ChannelImage``         (:455-682; ``_map_to_uint8`` / ``scale`` :493-568,
                             ``clip`` :570-597, ``_correct_illumination`` :599-631,
-                            ``correct`` :633-670)
+                            ``correct`` :633-670, ``png_encode`` :672-682)
   ``IllumstatsImage``      (:1097-1136)
   ``IllumstatsContainer``  (:1139-1213; ``smooth`` :1172-1193,
                             ``get_closest_percentile`` :1195-1213)
@@ -427,6 +427,99 @@ class ChannelImage(Image):
         new_object = ChannelImage(array, self.metadata)
         new_object.metadata.is_corrected = True
         return new_object
+
+    def png_encode(self):
+        """image.py:672-682: the image's PNG file as a 1-D uint8 array, coded
+        on the device (``tmh_png_encode`` over this one image;
+        ``png_encode_sites`` codes many in one call).  A standard greyscale PNG
+        of bit depth 8 or 16 that decodes to the pixels; its bytes are not those
+        ``cv2.imencode('.png', array)`` gets from libpng."""
+        a = self.array
+        if not (a.dtype == np.uint8 or a.dtype == np.uint16):
+            raise TypeError("Image must have 8-bit or 16-bit unsigned integer type.")
+        a = np.ascontiguousarray(a)
+        L = hip.lib()
+        out = np.empty(int(L.tmh_png_bound(a.shape[0], a.shape[1], a.itemsize)), dtype=np.uint8)
+        offsets = np.zeros(2, dtype=np.int64)
+        total = C.c_int64(0)
+        hip.check(L.tmh_png_encode(hip.ptr(a), 1, a.shape[0], a.shape[1], a.itemsize, hip.ptr(out),
+                                   out.nbytes, hip.ptr(offsets), C.byref(total)))
+        return out[:total.value].copy()
+
+
+class EncodedPngs(object):
+    """The PNG files of a batch of sites: ``blob`` (1-D uint8, host) holds them
+    back to back, site i's at ``offsets[i] : offsets[i + 1]`` (int64, sites + 1
+    entries)."""
+
+    def __init__(self, blob, offsets):
+        self.blob = blob
+        self.offsets = offsets
+
+    def file(self, i):
+        """The file of site i as ``bytes``."""
+        if not 0 <= i < len(self):
+            raise IndexError("file %d of %d" % (i, len(self)))
+        return self.blob[self.offsets[i]:self.offsets[i + 1]].tobytes()
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    def __iter__(self):
+        return (self.file(i) for i in range(len(self)))
+
+
+def png_encode_sites(sites) -> EncodedPngs:
+    """The PNG files of ``sites``, [n, H, W] or [H, W] uint8 / uint16, in one
+    ``tmh_png_encode_device`` call: a numpy array, or a device tensor (an int16
+    tensor is taken as the uint16 bits, as ``DeviceChunkEncoder.deflate`` does)
+    -- the uint8 sites ``Corrector.chain_u8`` leaves on the device are coded
+    without a host round trip.  No CPU fallback."""
+    L = hip.lib()
+    src = None
+    if isinstance(sites, np.ndarray):
+        if not (sites.dtype == np.uint8 or sites.dtype == np.uint16):
+            raise TypeError("sites must have 8-bit or 16-bit unsigned integer type.")
+        a = np.ascontiguousarray(sites)
+        shape, es = a.shape, a.itemsize
+    else:
+        import torch
+        if not isinstance(sites, torch.Tensor) or not sites.is_cuda:
+            raise TypeError("sites must be a numpy array or a device tensor")
+        if sites.dtype not in (torch.uint8, torch.int16, getattr(torch, "uint16", torch.int16)):
+            raise TypeError("sites must have 8-bit or 16-bit unsigned integer type (int16 bits).")
+        a = sites.contiguous()
+        shape, es = tuple(a.shape), a.element_size()
+    if len(shape) == 2:
+        shape = (1,) + tuple(shape)
+    if len(shape) != 3:
+        raise ValueError("sites must be [n, H, W] or [H, W]")
+    n, h, w = (int(v) for v in shape)
+    if n == 0:
+        return EncodedPngs(np.zeros(0, np.uint8), np.zeros(1, np.int64))
+    dst_bytes = n * int(L.tmh_png_bound(h, w, es))
+    scr_bytes = int(L.tmh_png_scratch_bytes(n, h, w, es))
+    if dst_bytes <= 0 or scr_bytes <= 0:
+        raise ValueError("sites must have positive height and width")
+    try:
+        if isinstance(a, np.ndarray):
+            src = hip.DeviceBuffer.from_array(a)
+            images = src
+        else:
+            import torch
+            torch.cuda.synchronize(a.device)  # the tensor's producers are through
+            images = C.c_void_p(a.data_ptr())
+        with hip.DeviceBuffer(dst_bytes) as d_dst, hip.DeviceBuffer(scr_bytes) as d_scr, \
+                hip.DeviceBuffer(8 * (n + 1)) as d_off:
+            hip.check(L.tmh_png_encode_device(images, n, h, w, es, d_dst, dst_bytes, d_off, d_scr,
+                                              scr_bytes, None))
+            hip.check(L.tmh_synchronize(None))
+            offsets = d_off.get((n + 1,), np.int64)
+            blob = d_dst.get((int(offsets[n]),), np.uint8)
+    finally:
+        if src is not None:
+            src.free()
+    return EncodedPngs(blob, offsets)
 
 
 def clip_array(array: np.ndarray, lower, upper) -> np.ndarray:
