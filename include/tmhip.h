@@ -915,6 +915,68 @@ int tmh_object_contours(const int32_t* host_planes, int64_t n_planes, int height
                         int32_t* host_points, int64_t point_capacity, int64_t* n_contours,
                         int64_t* n_points);
 
+/* Measurement (tmlib/workflow/jterator/handles.py:840-924): the intensity
+ * features of every object of a label plane, DESIGN.md section 27.  For label
+ * l of a plane and one channel, the values v = I[L == l] give one integer row
+ * (n == 0: all fields 0); max, mean, min, sum and std (np.std, ddof 0) follow
+ * from the rows bit for bit as section 27.1 states.  Every field is
+ * accumulated with integer atomics: exact, the same bytes from call to call.
+ * The table kernel keeps a 16 x 512 tile's labels in an LDS hash of
+ * TMH_INTENSITY_SLOTS entries (the top 9 bits of label * 2654435761 mod 2^32,
+ * linear probing, TMH_INTENSITY_PROBE probes); a label that finds no entry is
+ * added to its rows in memory directly.  One pass holds up to
+ * TMH_INTENSITY_PASS_CHANNELS channels; more channels are more passes inside
+ * the call. */
+#define TMH_INTENSITY_SLOTS 512
+#define TMH_INTENSITY_PROBE 16
+#define TMH_INTENSITY_PASS_CHANNELS 4
+#define TMH_INTENSITY_MAX_CHANNELS 16
+typedef struct tmh_intensity_row {
+  uint64_t sum, sum_sq;  /* of the values, of their squares */
+  int64_t n;             /* pixel count */
+  uint32_t min, max;
+} tmh_intensity_row;
+/* dev_labels [n_planes][height][width] int32; pixel (channel c, plane p, row y,
+ * column x) is element c * channel_stride + p * plane_stride + y * row_stride
+ * + x * pix_stride of dev_pixels, elements of elem_bytes (1: uint8, 2: uint16)
+ * bytes, so [channel][plane][H][W] arrays and the channel stack's interleaved
+ * [site][h][w][slot] layout are both read in place (the caller owns every
+ * element the strides reach).  dev_rows [n_planes][max_label + 1][n_channels].
+ * dev_object_rows NULL: a negative label or a label above max_label is
+ * TMH_EINVAL with dev_rows untouched, found as tmh_object_table_device finds
+ * it (computed and waited for first).  dev_object_rows = what
+ * tmh_object_table_device wrote for the same planes and max_label: the range
+ * counts as checked and the planes are not read for it again; either way the
+ * kernel never writes for a label outside [0, max_label].  TMH_EINVAL by
+ * name: n_channels outside 1..TMH_INTENSITY_MAX_CHANNELS, elem_bytes other
+ * than 1 or 2, more than 65,535 planes, a negative stride, dev_pixels not
+ * aligned to elem_bytes, dev_rows overlapping an input.  n_planes = 0 does
+ * nothing.  Queued on `stream` (NULL: the default stream). */
+int tmh_intensity_table_device(const int32_t* dev_labels, const void* dev_pixels, int elem_bytes,
+                               int64_t n_planes, int height, int width, int n_channels,
+                               int64_t channel_stride, int64_t plane_stride, int64_t row_stride,
+                               int64_t pix_stride, int32_t max_label,
+                               const tmh_object_row* dev_object_rows, tmh_intensity_row* dev_rows,
+                               void* stream);
+/* dev_features f64 [n_groups][max_label + 1][n_channels][5]: max, mean, min,
+ * sum, std of the objects of each group of n_planes / n_groups consecutive
+ * planes (the z-planes of a time point are one 3-D object: their rows are
+ * merged first, empty rows skipped); NaN where the merged n is 0.  n_groups
+ * must divide n_planes.  Queued on `stream` (NULL: the default stream). */
+int tmh_intensity_features_device(const tmh_intensity_row* dev_rows, int64_t n_planes,
+                                  int64_t n_groups, int32_t max_label, int n_channels,
+                                  double* dev_features, void* stream);
+/* Host buffers, pixels in the plain layout [n_channels][n_planes][height]
+ * [width].  *max_label = the largest label of all planes; host_rows holds
+ * row_capacity rows, n_planes * (*max_label + 1) * n_channels needed: a smaller
+ * capacity (or host_rows NULL) is TMH_EINVAL with *max_label set and nothing
+ * written.  A negative label: TMH_EINVAL. */
+int tmh_intensity_table(const int32_t* host_labels, const void* host_pixels, int elem_bytes,
+                        int64_t n_planes, int height, int width, int n_channels,
+                        int32_t* max_label, tmh_intensity_row* host_rows, int64_t row_capacity);
+int tmh_intensity_features(const tmh_intensity_row* host_rows, int64_t n_planes, int64_t n_groups,
+                           int32_t max_label, int n_channels, double* host_features);
+
 /* Input, SegmentationImage.create_from_polygons (tmlib/image.py:740-776) for
  * every plane of a site in one call: the label planes of stored outlines.
  * points is int32 [n_points][2], the rings' vertices one after the other as

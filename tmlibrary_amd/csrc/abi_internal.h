@@ -311,6 +311,13 @@ bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes);
 void require_finite(const double* dev_x, int64_t n, int d, DBuf<unsigned long long>& cnt,
                     hipStream_t s);
 
+// label planes (abi_objects.hip): the argument checks every entry point that
+// takes them shares, and the largest and smallest label of all planes on the
+// host (waits for them)
+void check_planes_args(const void* planes, int64_t n_planes, int height, int width);
+void label_range(const int32_t* dev_planes, int64_t n_planes, int height, int width, hipStream_t s,
+                 int32_t* hi, int32_t* lo);
+
 // the host forms' staging: the table and the optional scaler on the device
 struct HostTable {
   DBuf<double> x, center, scale;

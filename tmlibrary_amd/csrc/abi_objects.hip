@@ -7,7 +7,7 @@
 
 namespace tmh {
 
-static void check_planes_args(const void* planes, int64_t n_planes, int height, int width) {
+void check_planes_args(const void* planes, int64_t n_planes, int height, int width) {
   TMH_CHECK(n_planes >= 0 && height > 0 && width > 0, TMH_EINVAL, "bad geometry");
   TMH_CHECK(n_planes <= 65535, TMH_EINVAL, "at most 65,535 label planes per call");
   TMH_CHECK(n_planes == 0 || planes, TMH_EINVAL, "planes pointer is NULL");
@@ -24,7 +24,7 @@ static void label_max_dev(const int32_t* dev_planes, int64_t n_planes, int heigh
 }
 
 // the largest and smallest label of all planes, on the host (waits for them)
-static void label_range(const int32_t* dev_planes, int64_t n_planes, int height, int width,
+void label_range(const int32_t* dev_planes, int64_t n_planes, int height, int width,
                         hipStream_t s, int32_t* hi, int32_t* lo) {
   DBuf<int32_t> mm;
   mm.alloc((size_t)(2 * n_planes));

@@ -458,6 +458,15 @@ void launch_label_minmax(const int32_t* planes, int64_t n_planes, int64_t npx, i
                          int32_t* d_min, hipStream_t s);
 void launch_object_table(const int32_t* planes, int64_t n_planes, int H, int W, int32_t max_label,
                          tmh_object_row* rows, hipStream_t s);
+// jterator intensity measurements (measure_kernels.hip): strides in elements of
+// elem_bytes (1 or 2) bytes; rows [n_planes][max_label + 1][n_channels];
+// out f64 [n_groups][max_label + 1][n_channels][5]
+void launch_intensity_table(const int32_t* labels, const void* pixels, int elem_bytes,
+                            int64_t n_planes, int H, int W, int n_channels, int64_t cs, int64_t ps,
+                            int64_t rs, int64_t xs, int32_t max_label, tmh_intensity_row* rows,
+                            hipStream_t s);
+void launch_intensity_features(const tmh_intensity_row* rows, int64_t n_planes, int64_t n_groups,
+                               int32_t max_label, int n_channels, double* out, hipStream_t s);
 // jterator object outlines (contour_kernels.hip): the count pass and scan,
 // then the write pass on the same arguments; the scratch lives across both
 struct ContourScratch {

@@ -151,6 +151,11 @@ SIGNATURES = {
                                         C.POINTER(_I64), C.POINTER(_I64), _P]),
     "tmh_object_contours": (_I, [_P, _I64, _I, _I, C.POINTER(C.c_int32), _P, _P, _I64, _P, _I64, _P,
                                  _I64, C.POINTER(_I64), C.POINTER(_I64)]),
+    "tmh_intensity_table_device": (_I, [_P, _P, _I, _I64, _I, _I, _I, _I64, _I64, _I64, _I64,
+                                        C.c_int32, _P, _P, _P]),
+    "tmh_intensity_features_device": (_I, [_P, _I64, _I64, C.c_int32, _I, _P, _P]),
+    "tmh_intensity_table": (_I, [_P, _P, _I, _I64, _I, _I, _I, C.POINTER(C.c_int32), _P, _I64]),
+    "tmh_intensity_features": (_I, [_P, _I64, _I64, C.c_int32, _I, _P]),
     "tmh_polygon_fill_device": (_I, [_P, _P, _P, _P, _I64, _I64, _I, _I, _I64, _I64, _P, _P]),
     "tmh_polygon_fill": (_I, [_P, _P, _P, _P, _I64, _I64, _I, _I, _I64, _I64, _P]),
     "tmh_column_census_device": (_I, [_P, _I64, _I, _P, _P, _P, _P, _P, _P, _P]),
@@ -208,6 +213,20 @@ assert OBJECT_ROW_DTYPE.itemsize == 48
 #: its probe limit; a label that finds no entry is added to its row in memory
 OBJECT_SLOTS = 512
 OBJECT_PROBE = 16
+
+
+#: struct tmh_intensity_row (include/tmhip.h): one (plane, label, channel) of an intensity table
+INTENSITY_ROW_DTYPE = np.dtype([("sum", np.uint64), ("sum_sq", np.uint64), ("n", np.int64),
+                                ("min", np.uint32), ("max", np.uint32)])
+assert INTENSITY_ROW_DTYPE.itemsize == 32
+#: TMH_INTENSITY_SLOTS / _PROBE: the intensity kernel's LDS hash entries per tile and its
+#: probe limit; TMH_INTENSITY_PASS_CHANNELS / _MAX_CHANNELS: channels per pass, per call
+INTENSITY_SLOTS = 512
+INTENSITY_PROBE = 16
+INTENSITY_PASS_CHANNELS = 4
+INTENSITY_MAX_CHANNELS = 16
+#: the five features of a row, in the order tmh_intensity_features writes them
+INTENSITY_FEATURES = ("max", "mean", "min", "sum", "std")
 
 
 #: struct tmh_contour (include/tmhip.h): one border of one object

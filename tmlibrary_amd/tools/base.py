@@ -353,6 +353,28 @@ class FeatureStore(object):
         order = np.argsort(ids, kind="stable")
         self._types[name] = (ids[order], list(feature_names), values[order])
 
+    def append_mapobjects(self, name, feature_names, values):
+        """Rows for new mapobjects of a type, which is created on first use:
+        -> their ids, issued above every existing id of the type, in the order
+        of ``values`` [n][n_features].  Feature names other than the type's
+        are refused."""
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        feature_names = list(feature_names)
+        if values.ndim != 2 or values.shape[1] != len(feature_names):
+            raise ValueError("values must have shape (n_mapobjects, n_features)")
+        if name not in self._types:
+            old_ids = np.zeros(0, dtype=np.int64)
+            old_values = np.zeros((0, len(feature_names)), dtype=np.float64)
+        else:
+            old_ids, names, old_values = self._types[name]
+            if names != feature_names:
+                raise ValueError('Feature names differ from those of mapobject type "%s".' % name)
+        first = int(old_ids.max()) + 1 if old_ids.size else 1
+        ids = np.arange(first, first + values.shape[0], dtype=np.int64)
+        self._types[name] = (np.concatenate([old_ids, ids]), feature_names,
+                             np.concatenate([old_values, values], axis=0))
+        return ids
+
     def _type(self, name):
         try:
             return self._types[name]

@@ -10,19 +10,29 @@ checks.  All planes of a value go through one ``tmh_object_table`` call
 ``tmh_polygon_fill`` call); the host only does the reference's last arithmetic
 on the integer sums and its choice of shell and holes.
 
-Not built: measurements and the decoding of WKB elements (geometries arrive
-as rings: ``image.polygon_ring``).
+``Measurement`` (:840-924) and ``SegmentedObjects.measurements`` /
+``add_measurement`` (:577-658) carry per-object feature frames, restated for
+pandas 2.3 / numpy 2.2 (``np.nan``; the caller's frame is never mutated);
+``workflow/jterator/measure.py`` fills them from the GPU.  pandas is imported
+where it is used, so importing the package does not need it.
+
+Not built: the decoding of WKB elements (geometries arrive as rings:
+``image.polygon_ring``).
 ``iter_points`` yields a plain ``(x, y)`` tuple where the reference builds a
 ``shapely.geometry.Point``, ``iter_polygons`` an ``image.ContourPolygon``.
 """
 from __future__ import annotations
 
 import collections
+import logging
+import re
 
 import numpy as np
 
 from tmlibrary_amd.image import (label_planes_from_polygons, object_contours, object_tables,
                                  polygons_of_plane)
+
+logger = logging.getLogger(__name__)
 
 
 class LabelImage(object):
@@ -178,5 +188,115 @@ class SegmentedObjects(LabelImage):
             raise TypeError('Attribute "represent_as_polygons" must have type bool.')
         self._represent_as_polygons = value
 
+    @property
+    def measurements(self):
+        """handles.py:577-588: one DataFrame per time point, the frames added
+        for it side by side."""
+        import pandas as pd
+        if self._features:
+            return [pd.concat(self._features[t], axis=1) for t in sorted(self._features.keys())]
+        return [pd.DataFrame()]
+
+    @measurements.setter
+    def measurements(self, value):
+        import pandas as pd
+        if not isinstance(value, list):
+            raise TypeError('Argument "measurements" must have type list.')
+        features = collections.defaultdict(list)
+        for i, v in enumerate(value):
+            if not isinstance(v, pd.DataFrame):
+                raise TypeError('Items of argument "measurements" must have type '
+                                'pandas.DataFrame.')
+            features[i] = [v]
+        self._features = features
+
+    def add_measurement(self, measurement):
+        """handles.py:605-658: per time point the frame is brought to
+        ``labels`` -- missing labels padded with NaN rows, of duplicated labels
+        the first kept, unknown labels removed -- and must then match them."""
+        if not isinstance(measurement, Measurement):
+            raise TypeError('Argument "measurement" must have type '
+                            'tmlib.workflow.jterator.handles.Measurement.')
+        labels = self.labels
+        for t, val in enumerate(measurement.value):
+            if len(val.index) < len(labels):
+                logger.warning('missing values for object type "%s" at time point %d',
+                               self.key, t)
+                val = val.copy()
+                for label in labels:
+                    if label not in val.index:
+                        logger.warning("add NaN values for missing object #%d", label)
+                        val.loc[label, :] = np.nan
+                val = val.sort_index()
+            elif len(val.index) > len(labels):
+                if len(np.unique(val.index)) < len(val.index):
+                    logger.warning('duplicate values for "%s" at time point %d',
+                                   measurement.name, t)
+                    logger.info("remove duplicates and keep first")
+                    val = val[~val.index.duplicated(keep="first")]
+                else:
+                    logger.warning('too many values for object type "%s" at time point %d',
+                                   self.key, t)
+                    unknown = [i for i in val.index if i not in labels]
+                    for i in unknown:
+                        logger.warning("remove values for object #%d", i)
+                    val = val.drop(unknown)
+            if len(val.index) != len(labels) or np.any(val.index.values != np.array(labels)):
+                raise ValueError('Labels of objects for "%s" at time point %d do not match!'
+                                 % (measurement.name, t))
+            if len(np.unique(val.columns)) != len(val.columns):
+                raise ValueError('Column names of "%s" at time point %d must be unique.'
+                                 % (measurement.name, t))
+            self._features[t].append(val)
+
     def __str__(self):
         return "<SegmentedObjects(name=%r, key=%r)>" % (self.name, self.key)
+
+
+class Measurement(object):
+    """handles.py:840-924: a list over time points of DataFrames with one row
+    per segmented object and one column per feature."""
+
+    _NAME_PATTERN = re.compile(r"^[A-Za-z0-9_-]+$")
+
+    def __init__(self, name, objects, objects_ref, channel_ref=None, help=""):
+        for arg, v, types in (("objects", objects, (str,)), ("objects_ref", objects_ref, (str,)),
+                              ("channel_ref", channel_ref, (str, type(None)))):
+            if not isinstance(v, types):
+                raise TypeError('Argument "%s" must have type %s.'
+                                % (arg, " or ".join(t.__name__ for t in types)))
+        self.name = name
+        self.help = help
+        self.objects = objects
+        self.objects_ref = objects_ref
+        self.channel_ref = channel_ref
+
+    @property
+    def type(self):
+        return self.__class__.__name__
+
+    @property
+    def value(self):
+        return self._value
+
+    @value.setter
+    def value(self, value):
+        import pandas as pd
+        if not isinstance(value, list):
+            raise TypeError('Value of key "%s" must have type list.' % self.name)
+        if not all([isinstance(v, pd.DataFrame) for v in value]):
+            raise TypeError('Elements of returned value of "%s" must have type '
+                            'pandas.DataFrame.' % self.name)
+        for v in value:
+            for name in v.columns:
+                if not self._NAME_PATTERN.search(name):
+                    raise ValueError('Feature name "%s" must only contain '
+                                     'alphanumerical characters or underscores or hyphens' % name)
+        self._value = value
+
+    def to_dict(self):
+        return {"name": self.name, "objects": self.objects, "objects_ref": self.objects_ref,
+                "channel_ref": self.channel_ref, "type": self.type, "help": self.help}
+
+    def __str__(self):
+        return "<Measurement(name=%r, objects=%r)>" % (self.name, self.objects)
