@@ -823,11 +823,12 @@ int tmh_correct_stack_u16(tmh_corrector* c, const uint16_t* host_in, uint16_t* h
  * (mh.center_of_mass(plane, labels=plane)) and is_border, one row per label
  * 0..max_label of one int32 label plane [height][width] (label 0, the
  * background, gets a row like any other; mahotas does the same).  Every field
- * is exact and independent of scheduling.  The table kernel gathers each
- * 16 x 512 tile's labels in an LDS hash of TMH_OBJECT_SLOTS entries (the top
- * 9 bits of label * 2654435761 mod 2^32, linear probing); a label that finds
- * no entry within TMH_OBJECT_PROBE probes is added to its row in memory
- * directly: slower, the same result. */
+ * is exact and independent of scheduling.  How a table kernel walks a label
+ * plane, here and for the intensity table below: it gathers each 16 x 512
+ * tile's labels in an LDS hash of TMH_OBJECT_SLOTS entries (the top 9 bits of
+ * label * 2654435761 mod 2^32, linear probing); a label that finds no entry
+ * within TMH_OBJECT_PROBE probes is added to its row in memory directly:
+ * slower, the same result. */
 #define TMH_OBJECT_SLOTS 512
 #define TMH_OBJECT_PROBE 16
 typedef struct tmh_object_row {
@@ -921,12 +922,10 @@ int tmh_object_contours(const int32_t* host_planes, int64_t n_planes, int height
  * (n == 0: all fields 0); max, mean, min, sum and std (np.std, ddof 0) follow
  * from the rows bit for bit as section 27.1 states.  Every field is
  * accumulated with integer atomics: exact, the same bytes from call to call.
- * The table kernel keeps a 16 x 512 tile's labels in an LDS hash of
- * TMH_INTENSITY_SLOTS entries (the top 9 bits of label * 2654435761 mod 2^32,
- * linear probing, TMH_INTENSITY_PROBE probes); a label that finds no entry is
- * added to its rows in memory directly.  One pass holds up to
- * TMH_INTENSITY_PASS_CHANNELS channels; more channels are more passes inside
- * the call. */
+ * The table kernel walks the label plane as the object table's does (above),
+ * with TMH_INTENSITY_SLOTS entries and TMH_INTENSITY_PROBE probes, the same
+ * numbers.  One pass holds up to TMH_INTENSITY_PASS_CHANNELS channels; more
+ * channels are more passes inside the call. */
 #define TMH_INTENSITY_SLOTS 512
 #define TMH_INTENSITY_PROBE 16
 #define TMH_INTENSITY_PASS_CHANNELS 4

@@ -51,13 +51,19 @@ def many_labels_tile(n_labels=700):
 
 
 def bucket_of(label, slots):
-    """the LDS entry include/tmhip.h documents: the top bits of label * 2654435761 mod 2^32"""
+    """The LDS entry a label hashes to in both table kernels (label_tile.h, as
+    include/tmhip.h documents it): the top log2(slots) bits of the label times
+    the constant below, mod 2**32.  The hash restated here is a condition on
+    the input: with another hash the labels of same_bucket_labels would spread
+    over the table and the probe-limit tests would pass without reaching the
+    probe limit."""
     bits = slots.bit_length() - 1
     assert 1 << bits == slots
     return ((label * 2654435761) & 0xFFFFFFFF) >> (32 - bits)
 
 
 def same_bucket_labels(bucket, count, slots):
+    """the first `count` labels (from 1) whose LDS entry is `bucket`"""
     out, label = [], 1
     while len(out) < count:
         if bucket_of(label, slots) == bucket:

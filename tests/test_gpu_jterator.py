@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import intensity_cases as ic
 import objects_literal as lit
 
 pytestmark = pytest.mark.gpu
@@ -364,22 +365,6 @@ def test_objects_mixed_routes_across_tiles(L):
         assert got[p]["border"][edge].all() and int(got[p]["border"].sum()) == len(edge)
 
 
-def same_bucket_labels(bucket, count):
-    """The first `count` labels whose LDS hash is `bucket`.  The hash restated
-    here ((label * 2654435761 mod 2**32) >> (32 - log2(slots)), objects_kernels.hip)
-    is a condition on the input: with another hash the labels would spread over
-    the table and the test would pass without reaching the probe limit."""
-    from tmlibrary_amd import hip
-    bits = hip.OBJECT_SLOTS.bit_length() - 1
-    assert 1 << bits == hip.OBJECT_SLOTS
-    out, label = [], 0
-    while len(out) < count:
-        label += 1
-        if ((label * 2654435761) & 0xFFFFFFFF) >> (32 - bits) == bucket:
-            out.append(label)
-    return out
-
-
 def test_objects_probe_limit_in_a_nearly_empty_table(L):
     """k_object_table's probe loop giving up (t == kObjProbe) with the table
     almost empty: TMH_OBJECT_PROBE + 8 labels hash to entry 7 of one tile, the
@@ -388,7 +373,7 @@ def test_objects_probe_limit_in_a_nearly_empty_table(L):
     each (2 x 3 blocks: the second add meets the first's bounds, not the
     initial ones)."""
     from tmlibrary_amd import hip
-    labels = same_bucket_labels(7, hip.OBJECT_PROBE + 8)
+    labels = ic.same_bucket_labels(7, hip.OBJECT_PROBE + 8, hip.OBJECT_SLOTS)
     if hip.OBJECT_SLOTS == 512:
         assert labels[:5] == [267, 644, 1254, 1864, 2241]
     plane = np.zeros((16, 512), np.int32)

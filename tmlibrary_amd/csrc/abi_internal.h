@@ -312,11 +312,30 @@ void require_finite(const double* dev_x, int64_t n, int d, DBuf<unsigned long lo
                     hipStream_t s);
 
 // label planes (abi_objects.hip): the argument checks every entry point that
-// takes them shares, and the largest and smallest label of all planes on the
-// host (waits for them)
+// takes them shares, and the check of their labels -- the largest label of all
+// planes (waits for it); TMH_EINVAL when a label is negative or above max_label
 void check_planes_args(const void* planes, int64_t n_planes, int height, int width);
-void label_range(const int32_t* dev_planes, int64_t n_planes, int height, int width, hipStream_t s,
-                 int32_t* hi, int32_t* lo);
+int32_t check_label_range(const int32_t* dev_planes, int64_t n_planes, int height, int width,
+                          int32_t max_label, hipStream_t s);
+
+// The host forms' staging of label planes, after check_planes_args, in two
+// steps, because a form may have checks of its own that come between them:
+// has_label_planes sets *max_label = 0 and is false when there are no planes;
+// HostLabels::upload puts them on the device, rejects a negative label and
+// returns *max_label, their largest.
+inline bool has_label_planes(int64_t n_planes, int32_t* max_label) {
+  TMH_CHECK(max_label, TMH_EINVAL, "max_label pointer is NULL");
+  *max_label = 0;
+  return n_planes != 0;
+}
+struct HostLabels {
+  DBuf<int32_t> dev;
+  int32_t upload(const int32_t* host_planes, int64_t n_planes, int height, int width,
+                 int32_t* max_label) {
+    dev.upload(host_planes, (size_t)n_planes * height * width);
+    return *max_label = check_label_range(dev.p, n_planes, height, width, INT32_MAX, nullptr);
+  }
+};
 
 // the host forms' staging: the table and the optional scaler on the device
 struct HostTable {

@@ -44,12 +44,8 @@ static void intensity_table_dev(const int32_t* dev_labels, const void* dev_pixel
                 !overlap(dev_rows, row_bytes, dev_labels,
                          (size_t)n_planes * height * width * sizeof(int32_t)),
             TMH_EINVAL, "dev_rows overlaps an input");
-  if (!range_known) {
-    int32_t hi, lo;
-    label_range(dev_labels, n_planes, height, width, (hipStream_t)stream, &hi, &lo);
-    TMH_CHECK(lo >= 0, TMH_EINVAL, "a label plane holds a negative label");
-    TMH_CHECK(hi <= max_label, TMH_EINVAL, "a label plane holds a label above max_label");
-  }
+  if (!range_known)
+    check_label_range(dev_labels, n_planes, height, width, max_label, (hipStream_t)stream);
   launch_intensity_table(dev_labels, dev_pixels, elem_bytes, n_planes, height, width, n_channels,
                          cs, ps, rs, xs, max_label, dev_rows, (hipStream_t)stream);
 }
@@ -107,17 +103,11 @@ int tmh_intensity_table(const int32_t* host_labels, const void* host_pixels, int
     check_channels(n_channels);
     TMH_CHECK(elem_bytes == 1 || elem_bytes == 2, TMH_EINVAL,
               "elem_bytes must be 1 (uint8) or 2 (uint16): float and int32 images are not measured");
-    TMH_CHECK(max_label, TMH_EINVAL, "max_label pointer is NULL");
-    *max_label = 0;
-    if (n_planes == 0) return;
+    if (!has_label_planes(n_planes, max_label)) return;
     TMH_CHECK(host_pixels, TMH_EINVAL, "pixels pointer is NULL");
     const int64_t npx = (int64_t)height * width;
-    DBuf<int32_t> labels;
-    labels.upload(host_labels, (size_t)(n_planes * npx));
-    int32_t hi, lo;
-    label_range(labels.p, n_planes, height, width, nullptr, &hi, &lo);
-    TMH_CHECK(lo >= 0, TMH_EINVAL, "a label plane holds a negative label");
-    *max_label = hi;
+    HostLabels labels;
+    const int32_t hi = labels.upload(host_labels, n_planes, height, width, max_label);
     const int64_t n_rows = intensity_rows(n_planes, hi, n_channels);
     TMH_CHECK(host_rows && row_capacity >= n_rows, TMH_EINVAL,
               "row capacity smaller than n_planes * (*max_label + 1) * n_channels rows");
@@ -125,7 +115,7 @@ int tmh_intensity_table(const int32_t* host_labels, const void* host_pixels, int
     pixels.upload(host_pixels, (size_t)(n_channels * n_planes * npx * elem_bytes));
     DBuf<tmh_intensity_row> rows;
     rows.alloc((size_t)n_rows);
-    intensity_table_dev(labels.p, pixels.p, elem_bytes, n_planes, height, width, n_channels,
+    intensity_table_dev(labels.dev.p, pixels.p, elem_bytes, n_planes, height, width, n_channels,
                         n_planes * npx, npx, width, 1, hi, true, rows.p, nullptr);
     TMH_HIP(hipStreamSynchronize(nullptr));
     rows.download(host_rows, (size_t)n_rows);

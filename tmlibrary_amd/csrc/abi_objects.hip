@@ -23,21 +23,22 @@ static void label_max_dev(const int32_t* dev_planes, int64_t n_planes, int heigh
                       (hipStream_t)stream);
 }
 
-// the largest and smallest label of all planes, on the host (waits for them)
-void label_range(const int32_t* dev_planes, int64_t n_planes, int height, int width,
-                        hipStream_t s, int32_t* hi, int32_t* lo) {
+int32_t check_label_range(const int32_t* dev_planes, int64_t n_planes, int height, int width,
+                          int32_t max_label, hipStream_t s) {
   DBuf<int32_t> mm;
   mm.alloc((size_t)(2 * n_planes));
   launch_label_minmax(dev_planes, n_planes, (int64_t)height * width, mm.p, mm.p + n_planes, s);
   std::vector<int32_t> h((size_t)(2 * n_planes));
   TMH_HIP(hipMemcpyAsync(h.data(), mm.p, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   TMH_HIP(hipStreamSynchronize(s));
-  *hi = INT_MIN;
-  *lo = INT_MAX;
+  int32_t hi = INT_MIN, lo = INT_MAX;
   for (int64_t p = 0; p < n_planes; ++p) {
-    *hi = std::max(*hi, h[(size_t)p]);
-    *lo = std::min(*lo, h[(size_t)(n_planes + p)]);
+    hi = std::max(hi, h[(size_t)p]);
+    lo = std::min(lo, h[(size_t)(n_planes + p)]);
   }
+  TMH_CHECK(lo >= 0, TMH_EINVAL, "a label plane holds a negative label");
+  TMH_CHECK(hi <= max_label, TMH_EINVAL, "a label plane holds a label above max_label");
+  return hi;
 }
 
 static void object_table_dev(const int32_t* dev_planes, int64_t n_planes, int height, int width,
@@ -47,12 +48,8 @@ static void object_table_dev(const int32_t* dev_planes, int64_t n_planes, int he
   TMH_CHECK(max_label >= 0, TMH_EINVAL, "max_label is negative");
   TMH_CHECK(n_planes == 0 || dev_rows, TMH_EINVAL, "rows pointer is NULL");
   if (n_planes == 0) return;
-  if (!range_known) {
-    int32_t hi, lo;
-    label_range(dev_planes, n_planes, height, width, (hipStream_t)stream, &hi, &lo);
-    TMH_CHECK(lo >= 0, TMH_EINVAL, "a label plane holds a negative label");
-    TMH_CHECK(hi <= max_label, TMH_EINVAL, "a label plane holds a label above max_label");
-  }
+  if (!range_known)
+    check_label_range(dev_planes, n_planes, height, width, max_label, (hipStream_t)stream);
   launch_object_table(dev_planes, n_planes, height, width, max_label, dev_rows,
                       (hipStream_t)stream);
 }
@@ -112,21 +109,15 @@ int tmh_object_table(const int32_t* host_planes, int64_t n_planes, int height, i
                      int32_t* max_label, tmh_object_row* host_rows, int64_t row_capacity) {
   return guard([&] {
     check_planes_args(host_planes, n_planes, height, width);
-    TMH_CHECK(max_label, TMH_EINVAL, "max_label pointer is NULL");
-    *max_label = 0;
-    if (n_planes == 0) return;
-    DBuf<int32_t> a;
-    a.upload(host_planes, (size_t)n_planes * height * width);
-    int32_t hi, lo;
-    label_range(a.p, n_planes, height, width, nullptr, &hi, &lo);
-    TMH_CHECK(lo >= 0, TMH_EINVAL, "a label plane holds a negative label");
-    *max_label = hi;
+    if (!has_label_planes(n_planes, max_label)) return;
+    HostLabels a;
+    const int32_t hi = a.upload(host_planes, n_planes, height, width, max_label);
     const int64_t n_rows = n_planes * ((int64_t)hi + 1);
     TMH_CHECK(host_rows && row_capacity >= n_rows, TMH_EINVAL,
               "row capacity smaller than n_planes * (*max_label + 1) rows");
     DBuf<tmh_object_row> rows;
     rows.alloc((size_t)n_rows);
-    object_table_dev(a.p, n_planes, height, width, hi, rows.p, nullptr, true);
+    object_table_dev(a.dev.p, n_planes, height, width, hi, rows.p, nullptr, true);
     TMH_HIP(hipStreamSynchronize(nullptr));
     rows.download(host_rows, (size_t)n_rows);
   });
@@ -157,21 +148,17 @@ int tmh_object_contours(const int32_t* host_planes, int64_t n_planes, int height
     *max_label = 0;
     *n_contours = *n_points = 0;
     if (n_planes == 0) return;
-    DBuf<int32_t> a;
-    a.upload(host_planes, (size_t)n_planes * height * width);
-    int32_t hi, lo;
-    label_range(a.p, n_planes, height, width, nullptr, &hi, &lo);
-    TMH_CHECK(lo >= 0, TMH_EINVAL, "a label plane holds a negative label");
-    *max_label = hi;
+    HostLabels a;
+    const int32_t hi = a.upload(host_planes, n_planes, height, width, max_label);
     const int64_t n_rows = contour_rows(n_planes, hi);
     DBuf<tmh_object_row> rows;
     rows.alloc((size_t)n_rows);
     DBuf<tmh_contour_object> objects;
     objects.alloc((size_t)n_rows);
-    object_table_dev(a.p, n_planes, height, width, hi, rows.p, nullptr, true);
+    object_table_dev(a.dev.p, n_planes, height, width, hi, rows.p, nullptr, true);
     // measure, check every capacity before anything is written, then fill
-    object_contours_dev(a.p, n_planes, height, width, hi, rows.p, objects.p, nullptr, 0, nullptr, 0,
-                        n_contours, n_points, nullptr);
+    object_contours_dev(a.dev.p, n_planes, height, width, hi, rows.p, objects.p, nullptr, 0,
+                        nullptr, 0, n_contours, n_points, nullptr);
     TMH_CHECK(host_rows && host_objects && row_capacity >= n_rows, TMH_EINVAL,
               "row capacity smaller than n_planes * (*max_label + 1) rows");
     TMH_CHECK(contour_capacity >= *n_contours && point_capacity >= *n_points &&
@@ -182,8 +169,8 @@ int tmh_object_contours(const int32_t* host_planes, int64_t n_planes, int height
     DBuf<int32_t> points;
     points.alloc((size_t)std::max<int64_t>(2 * *n_points, 2));
     int64_t nc = 0, np = 0;
-    object_contours_dev(a.p, n_planes, height, width, hi, rows.p, objects.p, contours.p, *n_contours,
-                        points.p, *n_points, &nc, &np, nullptr);
+    object_contours_dev(a.dev.p, n_planes, height, width, hi, rows.p, objects.p, contours.p,
+                        *n_contours, points.p, *n_points, &nc, &np, nullptr);
     rows.download(host_rows, (size_t)n_rows);
     objects.download(host_objects, (size_t)n_rows);
     if (nc) contours.download(host_contours, (size_t)nc);

@@ -3,31 +3,26 @@
 // max) of the intensity values under the label, and the five features taken
 // from the rows (intensity_core.h).  DESIGN.md section 27.
 //
-// The table kernel follows the object table (objects_kernels.hip): a workgroup
-// owns a tile of kIntRows x kIntCols pixels, a wave reads 64 consecutive
-// pixels of a row, runs of equal labels are found with one shuffle and one
-// ballot.  A run's sums have no closed form here, so the wave does a segmented
-// inclusive scan (sum, sum of squares, min, max per channel, through DPP moves;
-// steps no lane needs are skipped) and the LAST lane of each run, which then
-// holds the run's totals, updates the tile's LDS hash table: one entry per label with n
-// and, per channel of the pass, sum, sum_sq, min, max.  Used entries are
-// flushed with integer global atomics; a label that finds no entry within
-// kIntProbe probes updates memory directly.  Everything is an integer atomic:
-// exact, and the same bytes from call to call.
+// The table kernel walks the plane as label_tile.h describes: tiles, runs, an
+// LDS table per tile, memory for what the table cannot hold.  Its own part: a
+// run's sums have no closed form here, so the wave does a segmented inclusive
+// scan (sum, sum of squares, min, max per channel, through DPP moves; steps no
+// lane needs are skipped) and the LAST lane of each run, which then holds the
+// run's totals, updates the table: one entry per label with n and, per channel
+// of the pass, sum, sum_sq, min, max.
 //
 // Within a tile n <= 8,192, so a tile's sum (< 2^29) is kept in 32 bits and
 // only sum_sq (< 2^45) in 64.  A pass holds up to kIntPass channels (44 KB of
 // LDS at four); more channels are more passes, each reading the labels again.
-// Labels outside [0, max_label] are never written.
 #include <algorithm>
 #include <climits>
 
 #include "common.h"
 #include "intensity_core.h"
+#include "label_tile.h"
 
 namespace tmh {
 
-constexpr int kIntRows = 16, kIntCols = 512;  // a workgroup's tile
 constexpr int kIntSlots = TMH_INTENSITY_SLOTS;
 constexpr int kIntProbe = TMH_INTENSITY_PROBE;
 constexpr int kIntPass = TMH_INTENSITY_PASS_CHANNELS;
@@ -126,40 +121,32 @@ __global__ __launch_bounds__(256) void k_intensity_table(const IntensityJob a) {
   tmh_intensity_row* prow =
       a.rows + plane * ((int64_t)a.max_label + 1) * a.n_channels + a.c0;
   const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
-  const int r0 = ty * kIntRows, c0 = tx * kIntCols;
+  const int r0 = ty * kTileRows, c0 = tx * kTileCols;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  constexpr int kSegs = kIntCols / 64, kItems = kIntRows * kSegs, kWaves = 4;
-  // item i of the tile: row r0 + i / kSegs, columns c0 + 64 (i % kSegs) ..; wave
-  // wv takes items wv, wv + 4, ..., kIntBatch of them loaded before any is used
-  for (int i0 = wv; i0 < kItems; i0 += kWaves * kIntBatch) {
+  // kIntBatch of a wave's items are loaded before any is used
+  for (int i0 = wv; i0 < kTileItems; i0 += kTileWaves * kIntBatch) {
     int lab[kIntBatch];
     unsigned int val[kIntBatch][C];
 #pragma unroll
     for (int b = 0; b < kIntBatch; ++b) {
-      const int i = i0 + b * kWaves;
-      const int y = r0 + i / kSegs, x = c0 + (i % kSegs) * 64 + lane;
-      const bool valid = i < kItems && y < H && x < W;
-      lab[b] = valid ? img[(int64_t)y * W + x] : -1;
-      const int64_t at = (int64_t)y * a.rs + (int64_t)x * a.xs;
+      const TileItem it = tile_item(i0 + b * kTileWaves, r0, c0, lane, H, W);
+      const bool valid = it.valid;
+      lab[b] = valid ? img[(int64_t)it.y * W + it.x] : -1;
+      const int64_t at = (int64_t)it.y * a.rs + (int64_t)it.x * a.xs;
 #pragma unroll
       for (int j = 0; j < C; ++j)
         val[b][j] = (valid && j < nc) ? (unsigned int)pix[at + j * a.cs] : 0u;
     }
 #pragma unroll
     for (int b = 0; b < kIntBatch; ++b) {
-      const int i = i0 + b * kWaves;
-      const int y = r0 + i / kSegs, x = c0 + (i % kSegs) * 64 + lane;
-      const bool valid = i < kItems && y < H && x < W;  // the valid lanes are lanes 0 .. nv - 1
+      const bool valid = tile_item(i0 + b * kTileWaves, r0, c0, lane, H, W).valid;
       const int L = lab[b];
-      const int below = __shfl_up(L, 1, 64);
-      const bool head = valid && (lane == 0 || L != below);
-      const unsigned long long heads = __ballot(head);
-      const int nv = __popcll(__ballot(valid));
-      if (nv == 0) continue;  // the whole wave
+      const LabelRuns runs = label_runs(L, valid, lane);
+      if (runs.nv == 0) continue;  // the whole wave
       // the run of a lane starts at the highest head at or below it (lane 0 is one)
-      const unsigned long long upto = heads & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
+      const unsigned long long upto = runs.heads & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
       const int start = 63 - __clzll((long long)(upto | 1ull));
-      const bool tail = valid && (lane + 1 == nv || ((heads >> (lane + 1)) & 1ull));
+      const bool tail = valid && (lane + 1 == runs.nv || ((runs.heads >> (lane + 1)) & 1ull));
       unsigned int s[C], lo[C], hi[C];
       unsigned long long q[C];
 #pragma unroll
@@ -179,7 +166,7 @@ __global__ __launch_bounds__(256) void k_intensity_table(const IntensityJob a) {
       scan_step<0x143, C>(valid && lane >= 32 && start < 32, s, q, lo, hi);
       if (!tail || (unsigned)L > (unsigned)a.max_label) continue;
       const unsigned int len = (unsigned int)(lane - start + 1);
-      int h = (int)(((unsigned int)L * 2654435761u) >> 23);  // 9 bits
+      int h = label_slot(L);
       bool found = false;
       for (int t = 0; t < kIntProbe; ++t) {
         const int old = atomicCAS(&key[h], -1, L);
@@ -237,10 +224,8 @@ __global__ void k_intensity_features(const tmh_intensity_row* __restrict__ rows,
   for (int j = 0; j < 5; ++j) out[i * 5 + j] = f[j];
 }
 
-static_assert(kIntSlots == 512, "the hash keeps 9 bits");
-static_assert(kIntProbe >= 1 && kIntProbe < kIntSlots, "a probe sequence stays inside the table");
 static_assert(kIntPass == 4, "k_intensity_table is instantiated for 1, 2 and 4 channels");
-static_assert(kIntRows * kIntCols <= 65536, "a tile's sum of 16-bit values is kept in 32 bits");
+static_assert(kTileRows * kTileCols <= 65536, "a tile's sum of 16-bit values is kept in 32 bits");
 static_assert(sizeof(tmh_intensity_row) == 32, "tmh_intensity_row layout (include/tmhip.h)");
 
 template <typename T>
@@ -262,9 +247,9 @@ void launch_intensity_table(const int32_t* labels, const void* pixels, int elem_
   const int64_t n_rows = n_planes * ((int64_t)max_label + 1) * n_channels;
   const dim3 rg((unsigned)cdiv(n_rows, 256));
   hipLaunchKernelGGL(k_intensity_init, rg, dim3(256), 0, s, rows, n_rows);
-  IntensityJob job{labels, pixels, H, W, (int)cdiv(W, kIntCols), max_label, n_channels, 0, 0,
+  IntensityJob job{labels, pixels, H, W, (int)cdiv(W, kTileCols), max_label, n_channels, 0, 0,
                    cs, ps, rs, xs, rows};
-  const dim3 grid((unsigned)(job.tiles_x * (int)cdiv(H, kIntRows)), (unsigned)n_planes);
+  const dim3 grid((unsigned)(job.tiles_x * (int)cdiv(H, kTileRows)), (unsigned)n_planes);
   for (int c0 = 0; c0 < n_channels; c0 += kIntPass) {
     job.c0 = c0;
     job.nc = std::min(kIntPass, n_channels - c0);

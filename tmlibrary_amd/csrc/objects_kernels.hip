@@ -10,31 +10,20 @@
 // these are made of; every field is accumulated with integer atomics, so the
 // table is exact and independent of scheduling.
 //
-// Traffic.  A label plane is mostly runs of equal labels along a row, and one
-// atomic per pixel would run at the atomic rate, not HBM's.  So:
-//  * a wave reads 64 consecutive pixels of a row; run heads are the lanes whose
-//    label differs from the lower lane's (one shuffle, one ballot).  The columns
-//    of a run are consecutive, so its pixel count is the distance to the next
-//    head bit and its column sum an arithmetic series: no segmented scan is
-//    needed, the head lane has both in closed form; sum_y is y * n;
-//  * head lanes update a per-workgroup table in LDS (kObjSlots entries, open
-//    addressing on the label), not memory: a workgroup owns a tile of
-//    kObjRows x kObjCols pixels, which meets a few dozen to a few hundred
-//    labels, and flushes each entry once -- 8 global atomics per (label, tile)
-//    instead of per run.  A label that finds no slot within kObjProbe probes
-//    (a tile with more labels than the table holds) updates memory directly:
-//    slower, still exact.
-// Labels outside [0, max_label] are never written: the C-ABI rejects such a
-// plane from k_label_minmax's result before this kernel is launched, and the
-// kernel skips them on its own as well.
+// The table kernel walks the plane as label_tile.h describes: tiles, runs, an
+// LDS table per tile, memory for what the table cannot hold.  Its own part: the
+// columns of a run are consecutive, so its pixel count is the distance to the
+// next head bit and its column sum an arithmetic series -- no segmented scan is
+// needed, the run's HEAD lane has both in closed form; sum_y is y * n.  An entry
+// is flushed once: 8 global atomics per (label, tile) instead of per run.
 #include <algorithm>
 #include <climits>
 
 #include "common.h"
+#include "label_tile.h"
 
 namespace tmh {
 
-constexpr int kObjRows = 16, kObjCols = 512;  // a workgroup's tile
 constexpr int kObjSlots = TMH_OBJECT_SLOTS;   // LDS table entries (22.5 KB)
 constexpr int kObjProbe = TMH_OBJECT_PROBE;
 constexpr int kObjBatch = 4;                  // row segments loaded ahead per wave
@@ -131,39 +120,31 @@ __global__ __launch_bounds__(256) void k_object_table(const int32_t* __restrict_
   const int32_t* img = planes + plane * (int64_t)H * W;
   tmh_object_row* prow = rows + plane * ((int64_t)max_label + 1);
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int r0 = ty * kObjRows, c0 = tx * kObjCols;
+  const int r0 = ty * kTileRows, c0 = tx * kTileCols;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  constexpr int kSegs = kObjCols / 64, kItems = kObjRows * kSegs, kWaves = 4;
-  // item i of the tile: row r0 + i / kSegs, columns c0 + 64 (i % kSegs) ..; wave
-  // wv takes items wv, wv + 4, ..., kObjBatch of them loaded before any is used
-  for (int i0 = wv; i0 < kItems; i0 += kWaves * kObjBatch) {
+  // kObjBatch of a wave's items are loaded before any is used
+  for (int i0 = wv; i0 < kTileItems; i0 += kTileWaves * kObjBatch) {
     int lab[kObjBatch];
 #pragma unroll
     for (int b = 0; b < kObjBatch; ++b) {
-      const int i = i0 + b * kWaves;
-      const int y = r0 + i / kSegs, x = c0 + (i % kSegs) * 64 + lane;
-      lab[b] = (i < kItems && y < H && x < W) ? img[(int64_t)y * W + x] : -1;
+      const TileItem it = tile_item(i0 + b * kTileWaves, r0, c0, lane, H, W);
+      lab[b] = it.valid ? img[(int64_t)it.y * W + it.x] : -1;
     }
 #pragma unroll
     for (int b = 0; b < kObjBatch; ++b) {
-      const int i = i0 + b * kWaves;
-      const int y = r0 + i / kSegs, x = c0 + (i % kSegs) * 64 + lane;
-      const bool valid = i < kItems && y < H && x < W;  // the valid lanes are lanes 0 .. nv - 1
-      const int L = lab[b];
-      const int below = __shfl_up(L, 1, 64);
-      const bool head = valid && (lane == 0 || L != below);
-      const unsigned long long heads = __ballot(head);
-      const int nv = __popcll(__ballot(valid));
-      if (!head || (unsigned)L > (unsigned)max_label) continue;
-      const unsigned long long above = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
-      const int next = above ? __ffsll((long long)above) - 1 : nv;
+      const TileItem it = tile_item(i0 + b * kTileWaves, r0, c0, lane, H, W);
+      const int y = it.y, x = it.x, L = lab[b];
+      const LabelRuns runs = label_runs(L, it.valid, lane);
+      if (!runs.head || (unsigned)L > (unsigned)max_label) continue;
+      const unsigned long long above = lane == 63 ? 0ull : runs.heads & (~0ull << (lane + 1));
+      const int next = above ? __ffsll((long long)above) - 1 : runs.nv;
       const unsigned int len = (unsigned int)(next - lane);
       const int xe = x + (int)len - 1;
       const unsigned long long rsy = (unsigned long long)y * len;
       const unsigned long long rsx =
           (unsigned long long)x * len + (unsigned long long)len * (len - 1) / 2;
       const unsigned int border = (y == 0 || y == H - 1 || x == 0 || xe == W - 1) ? 1u : 0u;
-      int h = (int)(((unsigned int)L * 2654435761u) >> 23);  // 9 bits
+      int h = label_slot(L);
       bool found = false;
       for (int t = 0; t < kObjProbe; ++t) {
         const int old = atomicCAS(&key[h], -1, L);
@@ -195,8 +176,6 @@ __global__ __launch_bounds__(256) void k_object_table(const int32_t* __restrict_
   }
 }
 
-static_assert(kObjSlots == 512, "the hash keeps 9 bits");
-static_assert(kObjProbe >= 1 && kObjProbe < kObjSlots, "a probe sequence stays inside the table");
 static_assert(sizeof(tmh_object_row) == 48, "tmh_object_row layout (include/tmhip.h)");
 
 void launch_label_minmax(const int32_t* planes, int64_t n_planes, int64_t npx, int32_t* d_max,
@@ -218,7 +197,7 @@ void launch_object_table(const int32_t* planes, int64_t n_planes, int H, int W, 
   const int64_t n_rows = n_planes * ((int64_t)max_label + 1);
   const dim3 rg((unsigned)cdiv(n_rows, 256));
   hipLaunchKernelGGL(k_object_init, rg, dim3(256), 0, s, rows, n_rows);
-  const int tiles_x = (int)cdiv(W, kObjCols), tiles_y = (int)cdiv(H, kObjRows);
+  const int tiles_x = (int)cdiv(W, kTileCols), tiles_y = (int)cdiv(H, kTileRows);
   hipLaunchKernelGGL(k_object_table, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n_planes),
                      dim3(256), 0, s, planes, H, W, tiles_x, max_label, rows);
   hipLaunchKernelGGL(k_object_finalize, rg, dim3(256), 0, s, rows, n_rows);

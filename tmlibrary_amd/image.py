@@ -751,17 +751,23 @@ def correct_stack(corrector, planes: np.ndarray, site, slot, windows, n_sites: i
     return out
 
 
+def _int32_planes(planes):
+    """the int32 label planes [n, H, W], C-contiguous"""
+    a = np.ascontiguousarray(planes)
+    if a.dtype != np.int32 or a.ndim != 3:
+        raise TypeError("label planes must be an int32 array [n, H, W]")
+    return a
+
+
 def object_tables(planes: np.ndarray) -> np.ndarray:
     """The object tables of int32 label planes [n, H, W] in one call: a
     structured array [n, max_label + 1] of ``hip.OBJECT_ROW_DTYPE`` (pixel
     count, row and column sums, mh.labeled.bbox, border flag per label;
     max_label over all planes).  A negative label raises ValueError."""
-    a = np.ascontiguousarray(planes)
-    if a.dtype != np.int32 or a.ndim != 3:
-        raise TypeError("label planes must be an int32 array [n, H, W]")
+    a = _int32_planes(planes)
     L = hip.lib()
     n = a.shape[0]
-    if n == 0 or a.shape[1] == 0 or a.shape[2] == 0:
+    if a.size == 0:
         return np.zeros((n, 1), dtype=hip.OBJECT_ROW_DTYPE)
     mx = C.c_int32(0)
     per = 4096  # rows per plane of the first attempt; a larger table is sized from *max_label
@@ -783,12 +789,10 @@ def object_contours(planes: np.ndarray):
     and ``hip.CONTOUR_OBJECT_DTYPE``, contours of ``hip.CONTOUR_DTYPE`` in
     (plane, label, discovery) order, points int32 [n_points, 2] as (x, y) of
     each object's padded bounding-box mask.  A negative label raises ValueError."""
-    a = np.ascontiguousarray(planes)
-    if a.dtype != np.int32 or a.ndim != 3:
-        raise TypeError("label planes must be an int32 array [n, H, W]")
+    a = _int32_planes(planes)
     L = hip.lib()
     n = a.shape[0]
-    if n == 0 or a.shape[1] == 0 or a.shape[2] == 0:
+    if a.size == 0:
         return (np.zeros((n, 1), dtype=hip.OBJECT_ROW_DTYPE),
                 np.zeros((n, 1), dtype=hip.CONTOUR_OBJECT_DTYPE),
                 np.zeros(0, dtype=hip.CONTOUR_DTYPE), np.zeros((0, 2), dtype=np.int32))
