@@ -580,7 +580,8 @@ int tmh_jpeg_decode_tiles(const uint8_t* host_blob, const int64_t* host_offsets,
  * and the shift is the argmax of C in signed form: a lag d along an axis of
  * length L is d when d <= L / 2 (integer division), else d - L.  So (y, x)
  * means T[r, c] ~ R[r + y, c + x], the sign _shift_and_crop expects.  Ties go
- * to the lowest flat unsigned lag dy * W + dx; two constant images give (0, 0).
+ * to the lowest flat unsigned lag dy * W + dx; a pair in which either image is
+ * constant has C = 0 exactly and gives (0, 0) with peak 0.
  * C is computed in f32 by a 2-D FFT; an axis whose length has a prime factor
  * above 5 is zero-padded to a 5-smooth length >= 2 L - 1 and the linear
  * correlation folded back to period L.  A transformed line holds at most 4,096

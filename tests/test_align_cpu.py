@@ -4,6 +4,9 @@
   (tests/golden/make_align_goldens.py) and the literal residue assignment;
 * the numpy literal of the correlation (tests/xcorr_literal.py) against the
   direct sum;
+* tests/align_cases.py: the launch geometry of every plane case the GPU tests
+  run, the classes the table must cover, and the batches' planted shifts
+  under the literal;
 * the job dicts and errors of ``ImageRegistrator.create_run_batches``;
 * tmlibrary_amd/csrc/fft_core.h -- the exact per-line code the registration
   kernels run -- compiled with g++ (tests/fft_host.cpp) and compared with
@@ -19,6 +22,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import align_cases as ac
 import xcorr_literal as xl
 from util import REPO, load_golden
 from tmlibrary_amd.metadata import ChannelImageMetadata
@@ -95,6 +99,88 @@ def test_literal_sign_and_mapping():
     # ties: the lowest flat unsigned lag; two constant images are one big tie
     assert xl.shift(np.full((4, 6), 9, np.uint16), np.full((4, 6), 70, np.uint16)) == (0, 0)
     assert xl.shift_of_plane(np.array([[1.0, 3.0, 3.0], [3.0, 0.0, 3.0]])) == (0, 1)
+
+
+# ---- the GPU tests' case table and batches (tests/align_cases.py) --------------------
+@pytest.mark.parametrize("case", ac.PLANE_CASES, ids=ac.case_id)
+def test_plane_case_is_what_the_table_says(case):
+    """The launch geometry is the table's, and the complex64 yardstick of the
+    plane bound is positive (2x2 is exact in both precisions)."""
+    H, W = case.shape
+    g = ac.geometry(H, W)
+    assert (g.Mh, g.Mw, g.c, g.half_cols, g.groups) == \
+        (case.Mh, case.Mw, case.c, case.half_cols, case.groups), case.why
+    assert g.stride == g.Mh | 1 and g.chunk == 1
+    assert 4 * g.c * g.stride * 8 <= ac.LDS_BYTES
+    t, r = xl.blob_pair(case.shape, case.planted[0], case.planted[1], seed=7, dtype=case.dtype)
+    c = xl.plane(t, r)
+    assert c.max() > c.min()
+    ref = float(np.abs(xl.plane_c64(t, r) - c).max())
+    if case.shape == (2, 2):
+        assert ref == 0.0
+    else:
+        assert ref > 0.0
+
+
+def test_plane_cases_cover_every_class():
+    cases = ac.PLANE_CASES
+    assert len({c.shape for c in cases}) == len(cases) >= 18
+    assert {c.c for c in cases} == {1, 2, 4, 7, 8}
+    assert any(c.c == c.half_cols < 8 and c.c > 1 for c in cases)
+    assert {c.Mw % 2 for c in cases} == {0, 1}
+    assert any(c.Mw % 2 == 1 and c.Mw == c.shape[1] > 1 for c in cases)   # odd, unpadded
+    assert any(c.Mw % 2 == 1 and c.Mw > c.shape[1] for c in cases)        # padded to odd
+    assert {(c.Mh > c.shape[0], c.Mw > c.shape[1]) for c in cases} == \
+        {(False, False), (False, True), (True, False), (True, True)}
+    assert any(1 < c.groups < 8 for c in cases)
+    assert any(c.groups > 8 and c.groups % 8 for c in cases)
+    assert any(c.groups * c.c > c.half_cols for c in cases)                # padding slots
+    assert any(c.shape[0] == 1 for c in cases) and any(c.shape[1] == 1 for c in cases)
+    assert any(c.shape[1] > 256 for c in cases)
+    u8 = [c for c in cases if c.dtype == np.uint8]
+    assert len(u8) >= 4
+    assert any(max(c.shape) <= 64 for c in u8)                             # small
+    assert any((c.Mh, c.Mw) != c.shape for c in u8)                        # padded
+    assert any(c.shape[0] > 700 for c in u8)                               # tall
+
+
+def test_rolled_batch_gives_its_rolls():
+    """The 7-pair batch at a small shape, every pair under the literal; at
+    full size one pair (the others hold by the same construction)."""
+    targets, refs, ref_of, shifts = ac.rolled_batch((54, 64))
+    assert len(set(shifts)) == 7 and (0, 0) in shifts
+    assert any(dy < 0 for dy, _ in shifts) and any(dx < 0 for _, dx in shifts)
+    assert sorted(set(ref_of.tolist())) == [0, 1, 2]
+    planes = ac.literal_planes(targets, refs, ref_of)
+    for i in range(7):
+        assert np.allclose(planes[i], xl.plane(targets[i], refs[ref_of[i]]), rtol=0, atol=1e-6)
+        assert xl.peak_margin(planes[i]) > 0.5
+    assert ac.shifts_of_planes(planes).tolist() == [list(s) for s in shifts]
+    targets, refs, ref_of, shifts = ac.rolled_batch((2160, 2560))
+    assert targets.dtype == np.uint8 and targets.shape == (7, 2160, 2560)
+    assert all(np.count_nonzero(r) >= 38 for r in refs)
+    i = 4                                                                  # (-1, -12)
+    c = xl.plane(targets[i], refs[ref_of[i]])
+    assert xl.shift_of_plane(c) == shifts[i] and xl.peak_margin(c) > 0.5
+    for j in range(7):
+        assert np.array_equal(np.roll(targets[j], shifts[j], axis=(0, 1)), refs[ref_of[j]])
+
+
+def test_tiny_batch_gives_its_shifts():
+    """One pair more than a launch takes: the literal recovers every planted
+    shift, and each peak stands a whole span above the rest of its plane."""
+    targets, refs, ref_of, shifts = ac.tiny_batch()
+    n = len(targets)
+    assert n == len(refs) == ac.MAX_LAUNCH + 1 and ac.geometry(4, 4, n).chunk == ac.MAX_LAUNCH
+    assert sorted(ref_of.tolist()) == list(range(n)) and not np.array_equal(ref_of, np.arange(n))
+    assert {tuple(s) for s in shifts.tolist()} == {(a, b) for a in range(-1, 3) for b in range(-1, 3)}
+    planes = ac.literal_planes(targets, refs, ref_of)
+    got = ac.shifts_of_planes(planes)
+    bad = np.flatnonzero((got != shifts).any(axis=1))
+    assert bad.size == 0, "pair %d: literal %s, planted %s" % (bad[0], got[bad[0]], shifts[bad[0]])
+    flat = np.sort(planes.reshape(n, -1), axis=1)
+    margin = (flat[:, -1] - flat[:, -2]) / (flat[:, -1] - flat[:, 0])
+    assert np.abs(margin - 1.0).max() < 1e-12
 
 
 # ---- jobs ----------------------------------------------------------------------------

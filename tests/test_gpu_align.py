@@ -14,14 +14,21 @@ literal's argmax, exactly.
 Plane bound: |plane - literal| <= 4 x (numpy's complex64 form - literal) +
 1e-7 of the span; the margin is for another radix order, the two-for-one
 split and twiddle rounding, not for a wrong algorithm.
+
+test_plane_per_geometry applies that bound at every class of launch geometry
+the kernels' host code can pick (tests/align_cases.py); the batch tests pass
+one chunk, one launch and one k_reg_sums launch; the sums tests rest on a
+constant image's plane being exactly 0.0 only when its own sum reaches it.
 """
 import os
 
 import numpy as np
 import pytest
 
+import align_cases as ac
 import xcorr_literal as xl
 from oracle import corilla_oracle as orc
+from tmlibrary_amd import hip
 
 pytestmark = pytest.mark.gpu
 
@@ -149,6 +156,201 @@ def test_plane_against_literal(reg, shape, planted):
           % (shape[0], shape[1], err / span, ref / span, err / ref))
     assert err <= RATIO * ref + FLOOR * span
     assert xl.shift_of_plane(got) == reg.calculate_shift(t, r)
+
+
+def _plane_error(got, t, r, c):
+    """(error, yardstick, span) of a GPU plane against the literal ``c``."""
+    span = float(c.max() - c.min())
+    err = float(np.abs(got - c).max())
+    ref = float(np.abs(xl.plane_c64(t, r) - c).max())
+    return err, ref, span
+
+
+@pytest.mark.parametrize("case", ac.PLANE_CASES, ids=ac.case_id)
+def test_plane_per_geometry(reg, case):
+    """The whole plane, at every class of launch geometry reg_run can pick
+    (align_cases.PLANE_CASES; test_align_cpu.py holds the table to the rule).
+    No margin condition: the bound is on every value of the plane."""
+    t, r = xl.blob_pair(case.shape, case.planted[0], case.planted[1], seed=7, dtype=case.dtype)
+    c = xl.plane(t, r)
+    got = reg.xcorr_plane(t, r)
+    assert got.dtype == np.float32 and got.shape == case.shape
+    err, ref, span = _plane_error(got, t, r, c)
+    print("%dx%d %s plane (c = %d, %d groups): error %.3g, numpy complex64 %.3g of the span; "
+          "ratio %.2f" % (case.shape[0], case.shape[1], np.dtype(case.dtype).name, case.c,
+                          case.groups, err / span, ref / span, err / ref if ref else 0.0))
+    assert err <= RATIO * ref + FLOOR * span, case.why
+    assert xl.shift_of_plane(got) == reg.calculate_shift(t, r)
+    _, _, peak = reg.calculate_shifts(t, r, return_peak=True)
+    assert peak.dtype == np.float32 and peak[0].tobytes() == got.max().tobytes()
+
+
+def _as_tensor(a):
+    import torch
+    return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).cuda()
+
+
+def test_batch_longer_than_a_chunk(reg):
+    """7 full-size pairs where a launch holds 3: chunks of 3, 3 and 1 through
+    one Z, one candidate table and the per-pair offsets into targets, sums,
+    ref_of and results."""
+    H, W = 2160, 2560
+    L = hip.lib()
+    assert ac.geometry(H, W, 7).chunk == 3
+    assert 0 < L.tmh_register_scratch_bytes(7, 3, H, W) < 7 * H * W * 8
+    targets, refs, ref_of, shifts = ac.rolled_batch((H, W))
+    y, x, peak = reg.calculate_shifts(targets, refs, ref_of, return_peak=True)
+    assert list(zip(y.tolist(), x.tolist())) == shifts
+    singles = [reg.calculate_shifts(targets[i], refs[ref_of[i]], return_peak=True)
+               for i in range(7)]
+    assert [(int(s[0][0]), int(s[1][0])) for s in singles] == shifts
+    assert np.array([s[2][0] for s in singles]).tobytes() == peak.tobytes()
+    assert (peak > 0).all() and len(set(peak.tolist())) >= 3
+    dy, dx, dpeak = reg.calculate_shifts(_as_tensor(targets), _as_tensor(refs), ref_of,
+                                         return_peak=True)
+    assert np.array_equal(dy, y) and np.array_equal(dx, x) and dpeak.tobytes() == peak.tobytes()
+
+
+def test_more_pairs_than_one_launch_takes(reg):
+    """32,769 pairs of 4x4: one more than a rows/cols launch and than a
+    k_reg_sums launch takes, for targets and references alike."""
+    targets, refs, ref_of, _ = ac.tiny_batch()
+    n = len(targets)
+    assert n == 32769 and ac.geometry(4, 4, n).chunk == 32768
+    planes = ac.literal_planes(targets, refs, ref_of)
+    want = ac.shifts_of_planes(planes)
+    y, x, peak = reg.calculate_shifts(targets, refs, ref_of, return_peak=True)
+    got = np.stack([y, x], axis=1)
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert bad.size == 0, "%d pairs differ, the first is %d: gpu %s, literal %s" \
+        % (bad.size, bad[0], got[bad[0]], want[bad[0]])
+    # 200^2 * 15 / 16 in every pair; quarters and sixteenths of small integers are exact in f32
+    lit = planes.reshape(n, -1).max(axis=1)
+    assert np.array_equal(lit, np.full(n, 37500.0))
+    bad = np.flatnonzero(peak != lit.astype(np.float32))
+    assert bad.size == 0, "%d peaks differ, the first is %d: %r" % (bad.size, bad[0], peak[bad[0]])
+
+
+def test_sums_beyond_one_launch(reg):
+    """The sum of a target alone moves no plane that exact arithmetic can
+    see: wrong by e, it adds e * sum(R - mean R) = 0, and at 4x4 every mean is
+    a multiple of 1/16 and the f32 sum is zero as well.  At 3x5 the means are
+    fifteenths, R - mean R is rounded, and its f32 sum is not zero.  So here
+    one side of every pair is a constant image, whose plane is exactly 0.0
+    when its own sum reaches it (Z is purely imaginary or purely real, and the
+    single radix-3 and radix-5 passes keep its Hermitian halves bit for bit),
+    and the other side has 15 random pixels.  Image 32,768, which the second
+    k_reg_sums launch adds up, is the constant at the top of the type."""
+    n = 32769
+    assert ac.geometry(3, 5, n).chunk == 32768
+    rng = np.random.default_rng(17)
+    for dtype in (np.uint8, np.uint16):
+        top = np.iinfo(dtype).max
+        consts = np.empty((n, 3, 5), dtype)
+        consts[:] = rng.integers(1, top + 1, n).astype(dtype)[:, None, None]
+        consts[-1] = top
+        noise = rng.integers(0, top + 1, (n, 3, 5)).astype(dtype)
+        back = np.arange(n, dtype=np.int32)[::-1].copy()
+        for name, targets, refs in (("constant targets", consts, noise),
+                                    ("constant references", noise, consts)):
+            for ref_of in (None, back):
+                y, x, peak = reg.calculate_shifts(targets, refs, ref_of, return_peak=True)
+                bad = np.flatnonzero((y != 0) | (x != 0) | (peak != 0.0))
+                assert bad.size == 0, "%s, %s: %d pairs are not flat, the first is %d: (%d, %d), " \
+                    "peak %r" % (np.dtype(dtype).name, name, bad.size, bad[0], y[bad[0]],
+                                 x[bad[0]], peak[bad[0]])
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16])
+@pytest.mark.parametrize("shape", [(37, 53), (1, 65)])
+def test_sums_of_unaligned_images(reg, shape, dtype):
+    """Images 1 and 2 of these stacks start off a 16-byte boundary, so
+    k_reg_sums adds them up in its all-scalar loop.  A constant image minus its
+    exact mean is exactly zero and so is every plane it takes part in: a sum
+    that is off shows as a peak that is not 0.0."""
+    px = shape[0] * shape[1]
+    es = np.dtype(dtype).itemsize
+    assert (px * es) % 16 != 0 and (2 * px * es) % 16 != 0
+    top = np.iinfo(dtype).max
+    consts = np.stack([np.full(shape, v, dtype) for v in (7, top, top // 2 + 1)])
+    others = np.stack([np.full(shape, v, dtype) for v in (top - 1, 3, 100)])
+    blobs = np.stack([xl.blob_pair(shape, 0, 0, seed=70 + k, dtype=dtype)[1] for k in range(3)])
+    assert all(b.max() > b.min() for b in blobs)
+    order = np.array([2, 0, 1], np.int32)
+    for name, targets, refs in (("constant targets", consts, blobs),
+                                ("constant references", blobs, consts),
+                                ("constants", consts, others)):
+        for ref_of in (None, order):
+            y, x, peak = reg.calculate_shifts(targets, refs, ref_of, return_peak=True)
+            print(name, y.tolist(), x.tolist(), peak.tolist())
+            assert y.tolist() == [0, 0, 0] and x.tolist() == [0, 0, 0], name
+            assert peak.tobytes() == np.zeros(3, np.float32).tobytes(), (name, peak.tolist())
+    # blobs against blobs: each pair as in a call of its own, and at the literal's maximum
+    shifts = [(2, -3), (0, 4), (-1, 1)] if shape[0] > 1 else [(0, -3), (0, 4), (0, 1)]
+    targets = np.stack([xl.blob_pair(shape, dy, dx, seed=70 + int(k), dtype=dtype)[0]
+                        for (dy, dx), k in zip(shifts, order)])
+    y, x, peak = reg.calculate_shifts(targets, blobs, order, return_peak=True)
+    for i in range(3):
+        t, r = targets[i], blobs[order[i]]
+        sy, sx, speak = reg.calculate_shifts(t, r, return_peak=True)
+        assert (int(y[i]), int(x[i])) == (int(sy[0]), int(sx[0]))
+        assert peak[i].tobytes() == speak[0].tobytes(), (i, peak[i], speak[0])
+        c = xl.plane(t, r)
+        _, ref, span = _plane_error(np.zeros(shape, np.float32), t, r, c)
+        print("pair %d: peak %.9g, literal %.9g, yardstick %.3g" % (i, peak[i], c.max(), ref))
+        assert abs(float(peak[i]) - float(c.max())) <= RATIO * ref + FLOOR * span
+
+
+def test_device_entry_refusals(reg):
+    """What tmh_register_shifts_device and tmh_xcorr_plane_device refuse on
+    their own, each before any launch; the same buffers then register a pair."""
+    L = hip.lib()
+    H, W = 30, 40
+    t, r = xl.blob_pair((H, W), 3, -5, seed=7)
+    want, c = _checked_literal(t, r)
+    sb = int(L.tmh_register_scratch_bytes(1, 1, H, W))
+    assert sb > 0 and sb % 256 == 0
+    rot = np.zeros(1, np.int32)
+    y, x = np.full(1, 99, np.int32), np.full(1, 99, np.int32)
+    peak = np.full(1, -1.0, np.float32)
+    with hip.DeviceBuffer(t.nbytes + 2) as dt, hip.DeviceBuffer(r.nbytes + 2) as dr, \
+            hip.DeviceBuffer(sb + 256) as scratch, hip.DeviceBuffer(4 * H * W + 4) as plane:
+        assert scratch.value % 256 == 0 and plane.value % 4 == 0 and dt.value % 2 == 0
+        dt.put(t)
+        dr.put(r)
+        plane.put(np.full((H, W), -7.0, np.float32))
+
+        def shifts(tp=dt, rp=dr, sp=scratch, nbytes=sb):
+            return L.tmh_register_shifts_device(tp, 1, rp, 1, H, W, 2, hip.ptr(rot), sp, nbytes,
+                                                hip.ptr(y), hip.ptr(x), hip.ptr(peak), None)
+
+        def xplane(tp=dt, rp=dr, sp=scratch, nbytes=sb, pp=plane):
+            return L.tmh_xcorr_plane_device(tp, rp, H, W, 2, sp, nbytes, pp, None)
+
+        for call in (shifts, xplane):
+            for kwargs, words in (
+                    (dict(sp=None), ("scratch", "NULL")),
+                    (dict(sp=scratch.at(16, sb)), ("scratch", "aligned")),
+                    (dict(nbytes=sb - 1), ("scratch", "smaller")),
+                    (dict(tp=dt.at(1, t.nbytes)), ("images", "aligned")),
+                    (dict(rp=dr.at(1, r.nbytes)), ("images", "aligned"))):
+                rc = call(**kwargs)
+                msg = L.tmh_last_error().decode()
+                assert rc == hip.TMH_EINVAL, (call.__name__, kwargs, rc, msg)
+                assert all(w in msg for w in words), (call.__name__, kwargs, msg)
+        rc = xplane(pp=plane.at(2, 4 * H * W))
+        msg = L.tmh_last_error().decode()
+        assert rc == hip.TMH_EINVAL and "plane" in msg and "aligned" in msg, (rc, msg)
+        # nothing ran: no result and no plane value was written
+        assert (int(y[0]), int(x[0]), float(peak[0])) == (99, 99, -1.0)
+        assert np.array_equal(plane.get((H, W), np.float32), np.full((H, W), -7.0, np.float32))
+        hip.check(shifts())
+        assert (int(y[0]), int(x[0])) == want
+        hip.check(xplane())
+        got = plane.get((H, W), np.float32)
+        assert xl.shift_of_plane(got) == want and peak[0].tobytes() == got.max().tobytes()
+        err, ref, span = _plane_error(got, t, r, c)
+        assert err <= RATIO * ref + FLOOR * span
 
 
 @pytest.mark.parametrize("dy,dx", [(6, 9), (6, -9), (-6, 9), (-6, -9)])

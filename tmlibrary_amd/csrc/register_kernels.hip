@@ -83,13 +83,14 @@ __device__ inline Cand block_argmax(float v, int idx, Cand* smem) {
   return Cand{v, idx};
 }
 
-// integer sum of every image: grid (kSumParts, images)
+// integer sum and sum of squares of every image: grid (kSumParts, images)
 template <typename T>
 __global__ __launch_bounds__(256) void k_reg_sums(const T* __restrict__ imgs, int64_t px,
-                                                  unsigned long long* __restrict__ sums) {
+                                                  unsigned long long* __restrict__ sums,
+                                                  unsigned long long* __restrict__ squares) {
   const T* img = imgs + (int64_t)blockIdx.y * px;
   constexpr int kPer = 16 / sizeof(T);
-  unsigned long long acc = 0;
+  unsigned long long acc = 0, acc2 = 0;
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nthr = (int64_t)gridDim.x * blockDim.x;
   int64_t head = 0;
@@ -102,17 +103,41 @@ __global__ __launch_bounds__(256) void k_reg_sums(const T* __restrict__ imgs, in
       uint32_t s = 0;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        if (sizeof(T) == 2) s += (w[k] & 0xffffu) + (w[k] >> 16);
-        else s += (w[k] & 0xffu) + ((w[k] >> 8) & 0xffu) + ((w[k] >> 16) & 0xffu) + (w[k] >> 24);
+        if (sizeof(T) == 2) {
+          const uint32_t lo = w[k] & 0xffffu, hi = w[k] >> 16;
+          s += lo + hi;
+          acc2 += (unsigned long long)(lo * lo) + (hi * hi);  // each below 2^32, their sum not
+        } else {
+          const uint32_t b0 = w[k] & 0xffu, b1 = (w[k] >> 8) & 0xffu, b2 = (w[k] >> 16) & 0xffu,
+                         b3 = w[k] >> 24;
+          s += b0 + b1 + b2 + b3;
+          acc2 += b0 * b0 + b1 * b1 + b2 * b2 + b3 * b3;
+        }
       }
       acc += s;
     }
     head = nvec * kPer;
   }
-  for (int64_t i = head + tid; i < px; i += nthr) acc += img[i];
+  for (int64_t i = head + tid; i < px; i += nthr) {
+    const uint32_t v = img[i];
+    acc += v;
+    acc2 += v * v;
+  }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-  if ((threadIdx.x & 63) == 0 && acc) atomicAdd(&sums[blockIdx.y], acc);
+  for (int o = 32; o > 0; o >>= 1) {
+    acc += __shfl_down(acc, o, 64);
+    acc2 += __shfl_down(acc2, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0 && acc) {
+    atomicAdd(&sums[blockIdx.y], acc);
+    atomicAdd(&squares[blockIdx.y], acc2);
+  }
+}
+
+// every pixel equals the mean: px * sum(v^2) == sum(v)^2, in 128 bits
+__device__ inline bool reg_is_flat(unsigned long long sum, unsigned long long squares,
+                                   unsigned long long px) {
+  return squares * px == sum * sum && __umul64hi(squares, px) == __umul64hi(sum, sum);
 }
 
 // grid (H, pairs of the chunk); LDS 2 * Mw values
@@ -120,7 +145,8 @@ template <typename T>
 __global__ __launch_bounds__(kRowThreads) void k_reg_rows_fwd(
     const T* __restrict__ targets, const T* __restrict__ refs, const int32_t* __restrict__ ref_of,
     int64_t first_pair, int64_t n_targets, RegGeom g, const unsigned long long* __restrict__ sums,
-    const cf* __restrict__ tw_w, cf* __restrict__ Z) {
+    const unsigned long long* __restrict__ squares, const cf* __restrict__ tw_w,
+    cf* __restrict__ Z) {
   extern __shared__ __attribute__((aligned(16))) cf lds[];
   cf* src = lds;
   cf* dst = lds + g.Mw;
@@ -131,9 +157,15 @@ __global__ __launch_bounds__(kRowThreads) void k_reg_rows_fwd(
   const double mt = (double)sums[pair] / px, mr = (double)sums[n_targets + ri] / px;
   const T* trow = targets + (pair * g.H + r) * g.W;
   const T* rrow = refs + (ri * g.H + r) * g.W;
+  // A constant image correlates to exactly zero with anything, but the split of
+  // F(T) and F(R) from one transform is exact only up to rounding: the other
+  // image would leak into the flat one's spectrum and the argmax would be noise.
+  const unsigned long long npx = (unsigned long long)g.H * (unsigned long long)g.W;
+  const bool flat = reg_is_flat(sums[pair], squares[pair], npx) ||
+                    reg_is_flat(sums[n_targets + ri], squares[n_targets + ri], npx);
   for (int c = tid; c < g.Mw; c += kRowThreads)
-    src[c] = c < g.W ? cf{(float)((double)trow[c] - mt), (float)((double)rrow[c] - mr)}
-                     : cf{0.f, 0.f};
+    src[c] = c < g.W && !flat ? cf{(float)((double)trow[c] - mt), (float)((double)rrow[c] - mr)}
+                              : cf{0.f, 0.f};
   __syncthreads();
   int Ns = 1;
   for (int p = 0; p < g.pw.npass; ++p) {
@@ -319,7 +351,7 @@ RegScratch reg_scratch(const RegGeom& g, int64_t n, int64_t m) {
   };
   L.tw_h = take((size_t)g.Mh * sizeof(cf));
   L.tw_w = take((size_t)g.Mw * sizeof(cf));
-  L.sums = take((size_t)(n + m) * sizeof(unsigned long long));
+  L.sums = take(2 * (size_t)(n + m) * sizeof(unsigned long long));  // sums, then sums of squares
   L.ref_of = take((size_t)n * sizeof(int32_t));
   L.cand = take((size_t)L.chunk * g.H * sizeof(Cand));
   L.res = take((size_t)n * sizeof(RegResult));
@@ -334,22 +366,23 @@ void reg_run(const T* targets, int64_t n, const T* refs, int64_t m, const RegGeo
   const cf* tw_h = reinterpret_cast<const cf*>(scratch + L.tw_h);
   const cf* tw_w = reinterpret_cast<const cf*>(scratch + L.tw_w);
   auto* sums = reinterpret_cast<unsigned long long*>(scratch + L.sums);
+  unsigned long long* squares = sums + n + m;
   const int32_t* ref_of = reinterpret_cast<const int32_t*>(scratch + L.ref_of);
   Cand* cand = reinterpret_cast<Cand*>(scratch + L.cand);
   RegResult* res = reinterpret_cast<RegResult*>(scratch + L.res);
   cf* Z = reinterpret_cast<cf*>(scratch + L.z);
   const int64_t px = (int64_t)g.H * g.W;
 
-  TMH_HIP(hipMemsetAsync(sums, 0, (size_t)(n + m) * sizeof(unsigned long long), s));
+  TMH_HIP(hipMemsetAsync(sums, 0, 2 * (size_t)(n + m) * sizeof(unsigned long long), s));
   {
     ProfScope prof("reg_sums", s);
     const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(kSumParts, px / 4096));
     for (int64_t at = 0; at < n; at += 32768)
       hipLaunchKernelGGL(k_reg_sums<T>, dim3(parts, (unsigned)std::min<int64_t>(32768, n - at)),
-                         dim3(256), 0, s, targets + at * px, px, sums + at);
+                         dim3(256), 0, s, targets + at * px, px, sums + at, squares + at);
     for (int64_t at = 0; at < m; at += 32768)
       hipLaunchKernelGGL(k_reg_sums<T>, dim3(parts, (unsigned)std::min<int64_t>(32768, m - at)),
-                         dim3(256), 0, s, refs + at * px, px, sums + n + at);
+                         dim3(256), 0, s, refs + at * px, px, sums + n + at, squares + n + at);
     TMH_HIP(hipGetLastError());
   }
   const size_t row_lds = 2 * (size_t)g.Mw * sizeof(cf);
@@ -371,7 +404,7 @@ void reg_run(const T* targets, int64_t n, const T* refs, int64_t m, const RegGeo
     {
       ProfScope prof("reg_rows_fwd", s);
       hipLaunchKernelGGL(k_reg_rows_fwd<T>, dim3(g.H, pairs), dim3(kRowThreads), row_lds, s,
-                         targets, refs, ref_of, first, n, g, sums, tw_w, Z);
+                         targets, refs, ref_of, first, n, g, sums, squares, tw_w, Z);
       TMH_HIP(hipGetLastError());
     }
     {

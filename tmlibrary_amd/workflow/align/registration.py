@@ -58,7 +58,8 @@ def calculate_shifts(targets, references, ref_of_target=None, return_peak=False)
     (default: i, which needs n == m; one reference serves every target).
 
     Returns (y, x) int32 arrays of length n, and with ``return_peak`` the f32
-    correlation at the argmax.  Raises ValueError for shapes that differ and
+    correlation at the argmax; a pair in which either image is constant gives
+    (0, 0) and a peak of exactly 0.  Raises ValueError for shapes that differ and
     for an axis over the kernels' limit (a transformed line holds 4,096
     values: 4,096 for a 5-smooth length, 2,048 otherwise)."""
     t, n, H, W, es, t_dev = _stack(targets, "targets")
